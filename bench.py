@@ -9,7 +9,10 @@ assembly + solve + err + err_ext + the per-trajectory SPD flags the planner alwa
 the trajectories after (k mod 10) GN iterations from the straight-line initialisation ("10 GN iters"), precomputed
 before the timed region and resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+--dump-outputs DIR: after the timed regions rank 0 writes what the last timed step returned to its caller -- dtheta (B,n,d), err (B), err_ext (B)
+in float32 and the per-trajectory SPD flags `info` (B) as float64 -- and, N > 1, the gathered final trajectories, as DIR/<name>.npy; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 Before the W warm-up steps the GPU is brought to its steady clocks by a TIME-based pre-warm (>= 0.6 s of the same launches,
 reported as `prewarm_s`): a cold MI355X runs the first milliseconds ~12 % slower, and K = 20 steps last 0.2 ms.
 The timed region -- synchronise, EXACTLY K launches, synchronise -- is repeated R times (9 <= R <= 41, about 0.4 s in all; each
@@ -246,6 +249,26 @@ def cpu_blocktri(th_hist_cpu, start_cpu, goal_cpu, sdf_cpu, steps=5):
   return {'value': 1.0 / t, 'unit': 'GN steps/s (batch 4096)', 'cores': cores, 'cpu_model': cpu_model(), 'kind': 'port',
           'sample': 'block-tridiagonal fp64 C restatement (oracle/gn_blocktri.c), full 4096-trajectory batch, 1 warm-up + %d timed '
                     'steps, median %.4f s' % (steps, t)}
+
+
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+  """name -> tensor as out_dir/<name>.npy: float32 stays float32, every other dtype is written as float64.  Should the arrays exceed
+  DUMP_BUDGET_BYTES, every array of more than one row keeps the same fixed, seeded sample of its leading-dimension rows (a quarter of the budget
+  in all, so that the float64 row indices written beside each as out_dir/<name>_rows.npy fit too)."""
+  os.makedirs(out_dir, exist_ok=True)
+  host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+  host = {k: v if v.dtype == np.float32 else v.astype(np.float64) for k, v in host.items()}
+  total = sum(v.nbytes for v in host.values())
+  for k, v in host.items():
+    if total > DUMP_BUDGET_BYTES and v.ndim and v.shape[0] > 1:
+      keep = max(1, v.shape[0] * (DUMP_BUDGET_BYTES // 4) // total)
+      rows = np.sort(np.random.RandomState(seed).choice(v.shape[0], keep, replace=False))
+      np.save(os.path.join(out_dir, k + '_rows.npy'), rows.astype(np.float64))
+      v = v[rows]
+    np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(v))
 
 
 def prewarm(launch, seconds=PREWARM_S, chunk=400):
@@ -766,7 +789,9 @@ def main():
   ap.add_argument('--no-extras', action='store_true', help='skip the extra workload blocks (profiling runs)')
   ap.add_argument('--strong', action='store_true', help='BASELINE configs[4] literally: ONE batch of 32768 trajectories split over the N ranks (strong scaling; N = 1: all of it '
                                                         'on one GPU); the default is 4096 trajectories per rank (weak scaling, the metric BASELINE.json quotes)')
+  ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
   args = ap.parse_args()
+  if args.steps < 1: ap.error('--steps must be at least 1')
 
   world = int(os.environ.get('WORLD_SIZE', '1'))
   rank = int(os.environ.get('RANK', '0'))
@@ -795,7 +820,10 @@ def main():
     else: dist.init_process_group(backend, rank=rank, world_size=world)
 
   import __graft_entry__
-  if rank == 0: __graft_entry__.build()
+  # build() only where the library or the call trampoline is missing or older than its sources: a tree that was built beforehand may be read-only to the
+  # benchmarking process, and build() of earlier revisions creates its object directory even when there is nothing to compile
+  G = __graft_entry__
+  if rank == 0 and (G._stale(G.HIP_LIB, G.HIP_DEPS) or G._stale(G.PYCALL_LIB, G.PYCALL_DEPS)): G.build()
   if dist is not None: dist.barrier()
   from dgpmp2_amd import _capi, parallel
   from dgpmp2_amd.gpmp2.plan_layer import solver_config
@@ -878,6 +906,11 @@ def main():
     return time.perf_counter() - t0
 
   walls = np.asarray([region() for _ in range(R)])
+  # --dump-outputs: what the last timed step -- step(K - 1) of the last region -- handed back, copied on the stream before anything else launches into these buffers
+  dumped = None
+  if args.dump_outputs and rank == 0:
+    dumped = {'dtheta': dth.clone(), 'err': err.clone(), 'err_ext': eex.clone(), 'info': info.clone()}
+    if dist is not None: dumped['trajectories_gathered'] = gathered.clone()
   # a few more regions WITH events around the launches: the device-side span of a region (start-up of the first launch and gaps included)
   evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(9)]
   for a_, b_ in evs: a_.record(); b_.record()      # (a first record() of an event costs ~40 us of host time: not inside a region)
@@ -1005,6 +1038,8 @@ def main():
       hist_cpu = [t[:B_PER_GPU].cpu() for t in th_hist]
       out['cpu_baseline'] = cpu_baseline(hist_cpu, start[:B_PER_GPU].cpu(), goal[:B_PER_GPU].cpu(), sdf.cpu())
       out['cpu_baseline_blocktri'] = cpu_blocktri(hist_cpu, start[:B_PER_GPU].cpu(), goal[:B_PER_GPU].cpu(), sdf.cpu())
+    if dumped is not None:
+      dump_outputs(args.dump_outputs, dumped)
     print(json.dumps(out))
   if dist is not None:
     dist.barrier()
