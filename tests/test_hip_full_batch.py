@@ -3,7 +3,9 @@
 The every-kernel tests (tests/test_hip_every_kernel.py) run each instantiation on one or two wavefronts of smooth in-grid
 trajectories: no SIMD ever runs a second wavefront and the data-dependent branches take the same side in nearly every lane,
 so per-lane state that goes stale at a divergent join cannot show.  Here, for 2 robots x the 9 forced launch
-shapes x the 4 covariance modes (velocity limits on d = 4 in one mode per shape; exact fit and ragged lengths alternating),
+shapes x the 6 covariance modes (velocity limits on d = 4 in one of the first four modes per shape; exact fit and ragged lengths alternating;
+'static_diag' -- block elimination with C = 4 and without Woodbury -- and 'scalar' -- DGP_QC_SCALAR, the learned mode, also through the raw
+output vector -- at MIN_WAVES; lane_mix.configs) and one configuration per robot with per-sample grids of an odd size,
 on >= 2048 wavefronts per launch, the fp64 and the fp32 I/O kernels are held, per trajectory, to:
   (a) the C oracle's step (dtheta; err and err_ext per trajectory at 10 x TOL_ERR; info 0 except on the NaN trajectories);
   (b) the fused loop, K = 3 with tol_delta at the median first-step norm (iteration counts differ inside the wavefronts), against
@@ -20,6 +22,11 @@ on >= 2048 wavefronts per launch, the fp64 and the fp32 I/O kernels are held, pe
       whose bilinear cell, hinge or velocity-limit decisions change within +-h are excluded and counted.  The shared grid's gradient
       is left out of (e): it is a sum over the batch, held to the autograd oracle by the every-kernel tests;
   (f) NaN isolation: the wave neighbours of the NaN trajectories bit-equal to the same batch without the NaN.
+The twin families are held per trajectory to references as well, not only to themselves under rotation (a twin wrong the same way wherever the
+trajectory sits passes (c)): the step-errors twins against the same batch's step and unweighted_errors_batch at th + dtheta, their backward against
+its two halves run by hand; dgp_eval_errors (+ backward) against the C oracle, unweighted_errors_batch, autograd and a central difference; the tiled
+twins against the row-major kernels; the chain backward against the single-step backward launches walked through the traced history; the static
+kernel variant each static configuration launches against lane_mix.expected_variant.
 Part 3 of the same issue, test_hip_headline_ten_iterations_full_size: BASELINE configs[1..3] at B = 4096 x 64, 10 iterations (lane_mix.headline).
 A failure names the kernel's configuration, the trajectory, its wavefront and its lane offset."""
 import time
@@ -46,7 +53,15 @@ def test_hip_full_batch_lane_mixed(be, dof, lpt, monkeypatch):
     if l != lpt: continue
     monkeypatch.setenv('DGP_FORCE_SHAPE', '%d,%d' % (l, c))
     t0 = time.time()
-    bt = LM.make(dof, l, c, n, cov, vel=vel, seed=1000 * dof + 10 * l + c)
+    bt = LM.make(dof, l, c, n, cov, vel=vel, waves=LM.config_waves(cov), seed=1000 * dof + 10 * l + c)
+    rep = {}
+    bad += LM.run_config(be, bt, nthreads=NTHREADS, report=rep)      # (static modes: the kernel variant launched must be LM.expected_variant's)
+    print('full batch: %s: %.1f s %s' % (bt.tag, time.time() - t0, rep), flush=True)
+  l, c, n, cov, vel = LM.odd_config(dof)
+  if l == lpt:      # per-sample grids of an odd size: the tiled twins on padded tiles
+    monkeypatch.setenv('DGP_FORCE_SHAPE', '%d,%d' % (l, c))
+    t0 = time.time()
+    bt = LM.make(dof, l, c, n, cov, vel=vel, waves=LM.MIN_WAVES, seed=1000 * dof + 10 * l + c + 5, grid=LM.ODD_GRID)
     rep = {}
     bad += LM.run_config(be, bt, nthreads=NTHREADS, report=rep)
     print('full batch: %s: %.1f s %s' % (bt.tag, time.time() - t0, rep), flush=True)

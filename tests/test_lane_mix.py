@@ -1,7 +1,9 @@
 """CPU: the lane-mixed batches of tests/lane_mix.py and the checks of tests/test_hip_full_batch.py, before they reach a GPU.
   * coverage -- every configuration the GPU test runs has, in EVERY wavefront, a trajectory whose lanes take both sides of the
     hinge, states outside the grid, (C > 1) a lane with both sides inside its C states, (velocity limits) states on both sides of
-    the limit; and the K = 3 stopping rule gives two or more iteration counts in >= 90 % of the wavefronts (C oracle);
+    the limit; and the K = 3 stopping rule gives two or more iteration counts in >= 90 % of the wavefronts (C oracle; not for the
+    step-only 'scalar' modes); every static configuration launches lane_mix.expected_variant's kernel variant (emulator), and each robot
+    reaches block elimination with C = 4 and with C < 4 and both Woodbury variants;
   * sensitivity -- each planted fault (a host-side edit of a correct result) is reported by the checks;
   * pipeline -- the whole GPU test body on the CPU wavefront emulator at 3 wavefronts, one configuration per kernel family."""
 import os
@@ -9,6 +11,7 @@ import numpy as np
 import pytest
 import harness
 import parity_cases as PC
+from dgpmp2_amd import _capi
 import lane_mix as LM
 from oracle import blocktri as BT
 
@@ -21,10 +24,18 @@ def _valid(bt):
 
 
 @pytest.mark.parametrize('dof', [2, 3])
-def test_lane_mix_coverage(dof):
+def test_lane_mix_coverage(dof, monkeypatch):
   bad = []
-  for (lpt, c, n, cov, vel) in LM.configs(dof):
-    bt = LM.make(dof, lpt, c, n, cov, vel=vel, seed=1000 * dof + 10 * lpt + c)
+  reached = set()
+  for (lpt, c, n, cov, vel), grid in [(cf, None) for cf in LM.configs(dof)] + [(LM.odd_config(dof), LM.ODD_GRID)]:
+    if grid is None: bt = LM.make(dof, lpt, c, n, cov, vel=vel, waves=LM.config_waves(cov), seed=1000 * dof + 10 * lpt + c)
+    else: bt = LM.make(dof, lpt, c, n, cov, vel=vel, waves=LM.MIN_WAVES, seed=1000 * dof + 10 * lpt + c + 5, grid=grid)
+    want_v = LM.expected_variant(lpt, c, n, cov, vel)
+    if want_v is not None:      # the variant the same host dispatch picks under the forced shape
+      monkeypatch.setenv('DGP_FORCE_SHAPE', '%d,%d' % (lpt, c))
+      got = _capi.Solver(harness.config_from_oracle(bt.p, 'f64'), api=harness.emul_api()).step_kernel_variant(bt.B)
+      if got != want_v: bad.append('%s: static kernel variant %d, expected %d' % (bt.tag, got, want_v))
+      reached.add((got, c == 4) if got == 1 else got)
     T = LM.tpw(lpt)
     W = bt.waves + (T > 1)
     wave = np.arange(bt.B) // T
@@ -45,13 +56,15 @@ def test_lane_mix_coverage(dof):
       v = np.abs(bt.th_clean[:, :, dof:dof + 2]) >= 1.0
       both = v.reshape(bt.B, -1).any(1) & ~v.reshape(bt.B, -1).all(1)
       if not (np.bincount(wave[both], minlength=W) > 0).all(): bad.append('%s: wavefronts without mixed velocity limits' % bt.tag)
-    if T >= 2:      # the K = 3 stopping rule at tol_delta = median first-step norm: two or more iteration counts per wavefront
+    if T >= 2 and not LM.is_scalar(cov):      # the K = 3 stopping rule at tol_delta = median first-step norm: two or more iteration counts per wavefront
       ok = LM.ok_rows(bt)
       d0 = BT.gn_step(bt.p, bt.th, bt.start, bt.goal, bt.sdf, nthreads=NTHREADS, **LM.okw(bt))[0]
       tol = LM.median_tol(d0[ok])
       _, its, _ = LM.stopping(bt, LM.okw(bt), tol, 3, NTHREADS, 0.0)
       nd = np.array([len(set(its[(wave == w) & ok].tolist())) for w in range(W)])
       if not (nd >= 2).mean() >= 0.9: bad.append('%s: only %.1f %% of wavefronts with two iteration counts' % (bt.tag, 100 * (nd >= 2).mean()))
+  missing = {(1, True), (1, False), 3, 4} - reached
+  if missing: bad.append('dof %d: static kernel variants never reached: %s' % (dof, sorted(map(str, missing))))
   assert not bad, '\n'.join(bad)
 
 
@@ -82,13 +95,13 @@ def _grads(bt, idx):
   rs = np.random.RandomState(3)
   sub = lambda a: None if a is None else a[idx]
   gbar = rs.randn(len(idx), bt.n, 2 * bt.dof); gext = rs.randn(len(idx))
-  g = AT.step_gradients(bt.p, bt.th_clean[idx], bt.start[idx], bt.goal[idx], bt.sdf, gbar, gext, qc=sub(bt.qc), ow=sub(bt.ow), eps=sub(bt.eps), q_full=bt.q_full)
+  g = AT.step_gradients(bt.p, bt.th_clean[idx], bt.start[idx], bt.goal[idx], bt.sdf, gbar, gext, qc=sub(LM.oracle_qc(bt)), ow=sub(bt.ow), eps=sub(bt.eps), q_full=bt.q_full)
   return g, gbar, gext
 
 
 def _subbatch(bt, idx):
   s = LM.Batch(); s.__dict__.update(bt.__dict__)
-  for k in ('th', 'th_clean', 'start', 'goal', 'qc', 'ow', 'eps'):
+  for k in ('th', 'th_clean', 'start', 'goal', 'qc', 'ow', 'eps', 'qc_dense', 'raw_out'):
     a = getattr(bt, k); setattr(s, k, None if a is None else a[idx])
   s.th = s.th_clean      # (the NaN trajectory too, without its NaN)
   s.B = len(idx); s.nan_rows = np.zeros(0, np.int64)
@@ -140,17 +153,80 @@ def test_planted_nan_leak(small):
   assert msg and 'trajectory %d ' % (b + 1) in msg[0], msg
 
 
+def _round5(bt, a):
+  """the round-5 signature (profiles/r06_compiler_fault.md): row 0 of every lane >= 1 of EVERY trajectory off by 1e-3 -- wherever the trajectory sits"""
+  a = a.copy()
+  for j in range(1, -(-bt.n // bt.c)): a[:, j * bt.c] *= 1 + 1e-3
+  return a
+
+
+@pytest.mark.parametrize('what', ['step_errors dtheta', 'tiled backward g_th'])
+def test_planted_round5_signature(small, what):
+  """the same error in every trajectory: the new reference checks of the twins report it (naming a wavefront and a lane offset), the rotation check
+  cannot -- the gap the per-trajectory references close"""
+  bt, d, _, _ = small
+  ok = LM.ok_rows(bt)
+  if what == 'step_errors dtheta':
+    ref = PC.rnd(d, 'f32')
+    check = lambda got: LM.check_close(bt, '[f32] step_errors dtheta vs step', got, ref, LM.TWIN_STEP_TOL['f32'])
+  else:
+    idx = np.arange(bt.B)
+    g, _, _ = _grads(bt, idx)
+    ref = PC.rnd(g['th'].reshape(bt.th.shape), 'f32')
+    check = lambda got: LM.check_grads(bt, '[f32] [tiled] backward vs row-major', dict(th=got), dict(th=ref), LM.TILED_GRAD_TOL['f32'], ok)
+  assert not check(ref)
+  got = _round5(bt, ref)
+  msg = check(got)
+  assert msg and 'wavefront' in msg[0] and 'lane offset' in msg[0], msg
+  r = LM.tpw(bt.lpt) // 2 + 1
+  assert not LM.check_bit_equal(bt, what, got, np.roll(got, r, 0), r)      # (the rotated run is wrong the same way)
+
+
+def test_planted_unw_obs_error(small):
+  """a 1e-4 relative error in one trajectory's unw_obs against unweighted_errors_batch"""
+  bt = small[0]
+  ok = LM.ok_rows(bt) & ~LM.near_decision(bt, bt.th)
+  ref = LM.unweighted(bt, bt.th)[2]
+  assert (ref[ok] > 0).sum() > bt.B // 2
+  got = PC.rnd(ref, 'f32')
+  assert not LM.check_close(bt, 'unw_obs', got[:, None], ref[:, None], LM.UNW_TOL['f32'], rows=ok)
+  b = int(np.nonzero(ok & (ref > 0))[0][3])
+  got[b] = ref[b] * (1 + 1e-4)
+  msg = LM.check_close(bt, 'unw_obs', got[:, None], ref[:, None], LM.UNW_TOL['f32'], rows=ok)
+  assert msg and 'trajectory %d ' % b in msg[0], msg
+
+
+def test_planted_scalar_qc_lane_error():
+  """'scalar' mode: a 1e-3 error in one lane's block gradients g_qc -- caught by the lane-resolved directional check over g_qc"""
+  bt = LM.make(2, 16, 4, 64, 'scalar_diag', waves=6, seed=5)
+  idx = np.array([0, 1, 3, 5]) * LM.tpw(bt.lpt)
+  s = _subbatch(bt, idx)
+  g, gbar, gext = _grads(bt, idx)
+  grads = {k: g[k].reshape(LM.oracle_qc(s).shape if k == 'qc' else getattr(s, k).shape) for k in ('th', 'start', 'goal', 'qc', 'ow', 'eps')}
+  v = LM.lane_direction_qc(s, grads['qc'])
+  err, excl = LM.directional(s, grads, gbar, gext, v, nthreads=NTHREADS, h=LM.FD_H_QC)
+  assert not excl.any() and err.max() < LM.FD_LANE_TOL, err
+  lane = LM.probe_lane(s, 2)
+  grads['qc'] = grads['qc'].copy(); grads['qc'][2, lane * s.c:(lane + 1) * s.c] *= 1 + 1e-3
+  err2, _ = LM.directional(s, grads, gbar, gext, v, nthreads=NTHREADS, h=LM.FD_H_QC)
+  assert err2[2] > 5 * LM.FD_LANE_TOL and (np.delete(err2, 2) < LM.FD_LANE_TOL).all(), err2
+
+
 # ---- the GPU test body on the wavefront emulator ------------------------------------------------------------------------------------
 @pytest.mark.parametrize('cfg', [(2, 16, 4, 64, 'perstate', True),       # per-state Kronecker, velocity limits, step-errors + tiled twins
                                  (3, 32, 4, 125, 'static', False),       # Woodbury ragged, traced loop + chain backward, step-errors + tiled twins
                                  (2, 64, 1, 61, 'qfull', False),         # general (q_full), one trajectory per wavefront
-                                 (3, 16, 2, 32, 'static_full', False)],  # general static, traced loop
-                         ids=lambda c: 'dof%d_%d_%d_n%d_%s' % c[:5])
+                                 (3, 16, 2, 32, 'static_full', False),   # general static, traced loop
+                                 (2, 16, 4, 64, 'scalar_raw', False),    # DGP_QC_SCALAR through the raw output vector, step-errors + tiled twins
+                                 (3, 16, 4, 64, 'static_diag', False),   # block elimination at C = 4 (variant 1), traced loop + chain backward
+                                 (2, 32, 4, 125, 'perstate', True, LM.ODD_GRID)],      # per-sample grids of an odd size: the tiled twins on padded tiles
+                         ids=lambda c: 'dof%d_%d_%d_n%d_%s' % c[:5] + ('_grids' if len(c) > 6 else ''))
 def test_emulator_pipeline(cfg, monkeypatch):
-  dof, lpt, c, n, cov, vel = cfg
+  dof, lpt, c, n, cov, vel = cfg[:6]
   monkeypatch.setenv('DGP_FORCE_SHAPE', '%d,%d' % (lpt, c))
-  bt = LM.make(dof, lpt, c, n, cov, vel=vel, waves=3 if lpt < 64 else 5, seed=11)
+  bt = LM.make(dof, lpt, c, n, cov, vel=vel, waves=3 if lpt < 64 else 5, seed=11, grid=cfg[6] if len(cfg) > 6 else None)
   rep = {}
   bad = LM.run_config(harness.Backend('emul'), bt, nthreads=NTHREADS, report=rep)
   assert not bad, '\n'.join(bad[:40])
-  assert rep['fd_worst'] < LM.FD_TOL and rep['b_excluded'] <= 1, rep
+  assert rep['fd_worst'] < LM.FD_TOL and rep.get('b_excluded', 0) <= 1, rep
+  if LM.expected_variant(lpt, c, n, cov, vel) is not None: assert rep['variant'] == (LM.expected_variant(lpt, c, n, cov, vel), c), rep
