@@ -10,15 +10,16 @@ import argparse
 import json
 import os
 import shutil
-import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.join(ROOT, 'profiles', 'tools'))
-import isa_stats
+sys.path.insert(0, ROOT)
+from dgpmp2_amd._build import isa_stats, pipeline
+from dgpmp2_amd._build.units import UNITS
 
-CSRC = os.path.join(ROOT, 'dgpmp2_amd', 'csrc')
-ALL = ['%s_%s_g%d' % (d, t, g) for d in ('2', '3', '2t', '3t', '2e', '3e') for t in ('f32', 'f64') for g in (0, 1, 2, 3, 4)]      # (2t / 3t: the tiled twins, -DDGP_TL=1)
+INST = {u.name[len('gn_inst_'):]: u for u in UNITS if u.launcher}      # 2_f32_g0, 2t_f64_g3, 2e_f32_g1, ...: the gn_inst units of the product, by their short names
+ALL = sorted(INST)
 
 
 def main():
@@ -33,48 +34,29 @@ def main():
   for u in a.units: assert u in ALL, (u, ALL)
   work = os.path.join('/tmp', 'dgp_dev_' + a.o.replace('.', '_'))
   shutil.rmtree(work, ignore_errors=True); os.makedirs(work)
-  hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-  base = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c', '-save-temps=obj'] + ['-D' + d for d in a.D] + a.flag
-  jobs = []
-  for u in a.units:
-    dof, t, g = u.split('_')
-    d = os.path.join(work, u); os.makedirs(d)
-    jobs.append(base + (['-DDGP_TL=1'] if dof.endswith('t') else (['-DDGP_STEP_ERRS=1'] if dof.endswith('e') else [])) + ['-DDGP_INST_DOF=' + dof.rstrip('te'), '-DDGP_INST_F64=%d' % (t == 'f64'), '-DDGP_INST_GROUP=' + g[1], os.path.join(CSRC, 'gn_inst.hip'),
-                        '-o', os.path.join(d, u + '.o')])
-  d = os.path.join(work, 'abi'); os.makedirs(d)
-  jobs.append(base + [os.path.join(CSRC, 'dgpmp2_hip.hip'), '-o', os.path.join(d, 'abi.o')])
-  d = os.path.join(work, 'long'); os.makedirs(d)
-  jobs.append(base + [os.path.join(CSRC, 'gn_long_inst.hip'), '-o', os.path.join(d, 'long.o')])      # the long-trajectory kernels (small: always built)
-  d = os.path.join(work, 'edt'); os.makedirs(d)
-  jobs.append(base + [os.path.join(CSRC, 'sdf_edt.hip'), '-o', os.path.join(d, 'edt.o')])       # dgp_sdf_2d (the binding resolves every declared symbol)
+  hipcc = pipeline.hipcc_path()
+  # the units asked for, and the ones every library needs: the long-trajectory kernels (small), the C-ABI, dgp_sdf_2d (the binding resolves every declared symbol)
+  built = [INST[u] for u in a.units]
+  jobs = [pipeline.unit_job(u, work, ['-D' + d for d in a.D] + a.flag) for u in built + [u for u in UNITS if not u.launcher]]
   stub = os.path.join(work, 'stubs.hip')
-  with open(stub, 'w') as f:
-    f.write('#include "%s"\n' % os.path.join(CSRC, 'gn_device.h'))
-    for u in ALL:
-      if u not in a.units and not (u[1] == 'e' and u[-1] not in ('013' if u[0] == '2' else '03')):      # (the twin units the ABI references: groups 0, 3 and -- d = 4 -- 1)
-        f.write('hipError_t dgp_launch_%s(DgpShape, int, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t) { return hipErrorInvalidValue; }\n' % u)
-  d = os.path.join(work, 'stubs'); os.makedirs(d)
-  jobs.append([hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c', stub, '-o', os.path.join(d, 'stubs.o')])
-  # every unit through the product's own compile pipeline (__graft_entry__.compile_hip_unit: device assembly, the exec-join repair, assembler, bundler, host object);
-  # --raw: plain hipcc -c -save-temps (the unrepaired compiler output, for the reproducer builds of profiles/r06_compiler_fault.md)
-  sys.path.insert(0, ROOT)
-  import __graft_entry__ as G
-  from concurrent.futures import ThreadPoolExecutor
-  def one(j):
-    if a.raw or j[-3].endswith('stubs.hip'): return subprocess.call(j), None
-    flags = [x for x in j[1:-3] if x not in ('--offload-arch=gfx950', '-c', '-save-temps=obj')]
-    return 0, G.compile_hip_unit(hipcc, flags, j[-3], j[-1])
-  with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex: res = list(ex.map(one, jobs))
-  rcs = [r[0] for r in res]
-  if any(rcs): raise SystemExit('hipcc failed: %s' % rcs)
+  with open(stub, 'w') as f:      # every launcher of the product that is not built here (the ABI's launch tables reference them all)
+    f.write('#include "%s"\n' % os.path.join(pipeline.CSRC, 'gn_device.h'))
+    for u in UNITS:
+      if u.launcher and u not in built:
+        f.write('hipError_t %s(DgpShape, int, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t) { return hipErrorInvalidValue; }\n' % u.launcher)
+  stubs = pipeline.Job('stubs', stub, (), os.path.join(work, 'stubs', 'stubs.o'))
+  # every unit through the product's own compile pipeline (pipeline.compile_hip_unit: device assembly, the exec-join repair, assembler, bundler, host object);
+  # --raw: plain hipcc -c -save-temps (the unrepaired compiler output, for the reproducer builds of profiles/r06_compiler_fault.md); the stubs have no device code to repair
+  one = lambda j: pipeline.compile_job(hipcc, j, repair=not a.raw and j is not stubs)
+  with ThreadPoolExecutor(max_workers=pipeline.pool_size(len(jobs) + 1)) as ex: res = list(ex.map(one, jobs + [stubs]))      # (raises on the first failed unit)
   for j, r in zip(jobs, res):
-    if r[1] and (r[1][0] or r[1][1]): print('%-28s exec-join repair: %d instruction(s) moved, %d finding(s) left' % (os.path.basename(j[-1]), r[1][0], r[1][1]))
+    if r and (r[0] or r[1]): print('%-28s exec-join repair: %d instruction(s) moved, %d finding(s) left' % (os.path.basename(j.out), r[0], r[1]))
   out = os.path.join(ROOT, 'dgpmp2_amd', 'lib', a.o)
-  subprocess.check_call([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC'] + [j[-1] for j in jobs] + ['-o', out])
+  pipeline.link_shared(hipcc, jobs + [stubs], out)
   stats = {}
-  for u in a.units:
-    for fn in os.listdir(os.path.join(work, u)):
-      if fn.endswith('gfx950.s'): stats.update(isa_stats.parse(os.path.join(work, u, fn)))
+  for u in built:
+    for fn in os.listdir(os.path.join(work, u.name)):
+      if fn.endswith('gfx950.s'): stats.update(isa_stats.parse(os.path.join(work, u.name, fn)))
   json.dump(stats, open(out + '.stats.json', 'w'), indent=1, sort_keys=True)
   for k, v in sorted(stats.items()):
     if a.show in k:

@@ -21,16 +21,16 @@ echo "== control: the same function without the SGPR COPY in front of the exec r
 grep -v 'sgpr12_sgpr13 = COPY' "$M" | sed 's/\$sgpr12_sgpr13/$sgpr6_sgpr7/g' > "$W/control.mir"
 "$B/llc" -mtriple=amdgcn-amd-amdhsa -mcpu=gfx950 -run-pass=greedy -verify-machineinstrs "$W/control.mir" -o - 2>/dev/null | awk '/^  bb.2:/,/S_BRANCH/' | grep -E "SI_SPILL|S_OR_B64|COPY" | sed 's/, implicit.*//; s/ :: .*//'
 echo "== the MIR function compiled to assembly (-start-before=greedy) and the checker on it"
-"$B/llc" -mtriple=amdgcn-amd-amdhsa -mcpu=gfx950 -start-before=greedy "$M" -o "$W/mir.s" 2>/dev/null; python "$R/profiles/tools/exec_join_check.py" "$W/mir.s"
+"$B/llc" -mtriple=amdgcn-amd-amdhsa -mcpu=gfx950 -start-before=greedy "$M" -o "$W/mir.s" 2>/dev/null; PYTHONPATH="$R" python -m dgpmp2_amd._build.exec_join_check "$W/mir.s"
 echo "== (2) the IR of gn_kernel<2,16,2,float,STEP,general>"
 gzip -dc "$IRGZ" > "$W/one.ll"
 "$B/llc" --version | grep -i "version" | head -2
 "$B/llc" -mtriple=amdgcn-amd-amdhsa -mcpu=gfx950 -O3 "$W/one.ll" -o "$W/one.s" || exit 1
-python "$R/profiles/tools/exec_join_check.py" "$W/one.s"
+PYTHONPATH="$R" python -m dgpmp2_amd._build.exec_join_check "$W/one.s"
 echo "== which allocator runs it takes (llc switches; code size as a proxy for what the switch costs)"
 for o in "" "-sgpr-regalloc=basic" "-sgpr-regalloc=fast" "-vgpr-regalloc=basic"; do
   "$B/llc" -mtriple=amdgcn-amd-amdhsa -mcpu=gfx950 -O3 $o "$W/one.ll" -o "$W/alt.s" 2>/dev/null
-  echo "  [${o:-default: greedy / greedy}]  $(python "$R/profiles/tools/exec_join_check.py" "$W/alt.s" | tail -1)  $(grep -E '^; codeLenInByte' "$W/alt.s" | tr -d ';')"
+  echo "  [${o:-default: greedy / greedy}]  $(PYTHONPATH="$R" python -m dgpmp2_amd._build.exec_join_check "$W/alt.s" | tail -1)  $(grep -E '^; codeLenInByte' "$W/alt.s" | tr -d ';')"
 done
 echo "== the join block in the MIR: after the pass in front of the VGPR allocation run, and after that run (print-after=greedy, third dump)"
 "$B/llc" -mtriple=amdgcn-amd-amdhsa -mcpu=gfx950 -O3 "$W/one.ll" -o /dev/null -print-after=amdgpu-reserve-wwm-regs -print-after=greedy 2> "$W/pa.txt"

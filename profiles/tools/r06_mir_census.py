@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Round 6: an EXACT census of the exec-join spill placement (profiles/r06_compiler_fault.md) at the MIR level, for the translation units of the shipped library.
 
-exec_join_check.py works on the final assembly, where tail duplication and block placement blur which blocks are joins (a body's tail with a duplicated restore looks like a
+dgpmp2_amd/_build/exec_join_check.py works on the final assembly, where tail duplication and block placement blur which blocks are joins (a body's tail with a duplicated restore looks like a
 join top): it can prove the `store` class and must leave `reload`s in front of a restore as "reported".  Right after the VGPR run of the register allocator
 (`-mllvm -stop-after=greedy,2`) the blocks are still the structured ones: every `$exec = S_OR_B64 $exec, ...` at the top of a block IS the restore of a join, and every vector
 instruction in front of it in that block was put there by the allocator under the wrong mask.  Per unit: hipcc --cuda-device-only -S -mllvm -stop-after=greedy,2 (MIR instead of assembly) -> count, per

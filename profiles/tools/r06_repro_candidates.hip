@@ -1,5 +1,5 @@
 // Round 6: five hand-written candidates for a SMALL reproducer of the exec-join miscompile (profiles/r06_compiler_fault.md).  None of them triggers it:
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S profiles/tools/r06_repro_candidates.hip -o /tmp/c.s && python profiles/tools/exec_join_check.py /tmp/c.s   -> 0 findings
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S profiles/tools/r06_repro_candidates.hip -o /tmp/c.s && python -m dgpmp2_amd._build.exec_join_check /tmp/c.s   -> 0 findings
 // c4 / c5 do produce join blocks with lane-mask merges in front of the exec restore (the precondition); the allocator splits its live ranges elsewhere.  The reproducer is the
 // IR of a real kernel: profiles/tools/r06_llc_repro.sh.
 #include <hip/hip_runtime.h>

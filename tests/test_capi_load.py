@@ -27,6 +27,24 @@ def test_exports_every_declared_symbol(api):
   assert api.abi_version() == _capi.DGP_ABI_VERSION
 
 
+def test_launch_tables_reference_exactly_the_launchers_of_the_unit_table():
+  """The launch tables of dgpmp2_hip.hip and the unit table of the build (dgpmp2_amd/_build/units.py) are kept by hand and must agree: a launcher the tables name but no
+  unit defines fails the link, one a unit defines but no table names is dead weight.  gn_device.h declares every launcher of the tables, plus -- by the regularity of
+  DGP_DECL_INST -- ten step-errors launchers that are neither built nor called: groups 2 and 4 (backward kernels: no step to add an errors epilogue to) and d = 6 group 1
+  (the general twins units.py leaves out, with the measurement)."""
+  from dgpmp2_amd._build.units import LAUNCHERS
+  csrc = os.path.join(ROOT, 'dgpmp2_amd', 'csrc')
+  strip = lambda text: re.sub(r'//[^\n]*|/\*.*?\*/', '', text, flags=re.S)
+  referenced = set(re.findall(r'\bdgp_launch_[23][te]?_f(?:32|64)_g\d\b', strip(open(os.path.join(csrc, 'dgpmp2_hip.hip')).read())))
+  hdr = strip(open(os.path.join(csrc, 'gn_device.h')).read())
+  per_group = re.findall(r'dgp_launch_##d##_##t##_(g\d)\(', hdr[hdr.index('#define DGP_DECL_INST(d, t)'):hdr.index('#undef DGP_DECL_INST')])
+  declared = set('dgp_launch_%s_%s_%s' % (d, t, g) for d, t in re.findall(r'\bDGP_DECL_INST\(([23][te]?), (f32|f64)\)', hdr) for g in per_group)
+  assert len(LAUNCHERS) == len(set(LAUNCHERS)) == 50
+  assert referenced == set(LAUNCHERS)
+  declared_never_built = set('dgp_launch_%se_%s_g%d' % (d, t, g) for d, groups in ((2, (2, 4)), (3, (1, 2, 4))) for t in ('f32', 'f64') for g in groups)
+  assert declared - referenced == declared_never_built and referenced <= declared
+
+
 def test_struct_layout_matches_header():
   # sizes implied by the header on LP64: see DgpConfig/DgpSdf/DgpCovs in include/dgpmp2_hip.h
   assert C.sizeof(_capi.DgpConfig) == 6 * 4 + 8 * (1 + 2 + 2 + 2 + 1 + 1 + 9 + 1 + 1 + 1 + 3)
@@ -129,13 +147,12 @@ def test_step_kernel_variant_choice(api, monkeypatch):
 
 def test_spill_guard_every_heavy_spiller_was_verified_on_a_gpu():
   """hipcc has miscompiled these kernels six times, every time among the heaviest spillers.  A kernel at that spill
-  level (profiles/tools/spill_guard.py: >= 300 spilled VGPRs, >= 150 spilled SGPRs or >= 1 KB scratch per lane) must be listed, with its spill
+  level (dgpmp2_amd/_build/spill_guard.py: >= 300 spilled VGPRs, >= 150 spilled SGPRs or >= 1 KB scratch per lane) must be listed, with its spill
   counts, in dgpmp2_amd/csrc/spill_baseline.json -- which is only ever rewritten after tests/test_hip_every_kernel.py ran green on a GPU
   against the build that produced those counts.  A new or grown heavy spiller fails HERE, before it ships unverified."""
-  import json, os, sys
+  import json, os
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-  sys.path.insert(0, os.path.join(root, 'profiles', 'tools'))
-  import spill_guard
+  from dgpmp2_amd._build import spill_guard
   stats = json.load(open(os.path.join(root, 'dgpmp2_amd', 'lib', 'kernel_stats.json')))
   base = spill_guard.load_baseline()
   assert base, 'dgpmp2_amd/csrc/spill_baseline.json is missing or empty'
@@ -151,9 +168,8 @@ def test_exec_join_checker_and_repair(tmp_path):
   """Round 6: the static checker of the hipcc miscompile signature (profiles/r06_compiler_fault.md) and the repair the build applies, on a synthetic kernel:
   a spill store at the top of a join block in front of the exec restore is found and moved behind it; the body of the `if`, an out-of-line body, a slot that
   holds an earlier unconsumed write (`merge`) and a reload whose register is rewritten are left alone; the built library's record carries no surviving finding."""
-  import json, sys
-  sys.path.insert(0, os.path.join(ROOT, 'profiles', 'tools'))
-  import exec_join_check as CK, exec_join_patch as P
+  import json
+  from dgpmp2_amd._build import exec_join_check as CK, exec_join_patch as P
   asm = '''
 _Z6kernelv:
 	v_accvgpr_write_b32 a7, v9
@@ -205,9 +221,7 @@ def test_exec_join_checker_tells_joins_from_body_tails(tmp_path):
   """Second pass of round 6: (1) the last block of an `if` body in front of a tail-duplicated restore is NOT a join -- its register saves belong to the body's lanes (the first
   checker `repaired` such an exit shuffle in a shipped kernel); (2) an `if` without a skip branch joins in the fall-through block that restores from its saved mask;
   (3) a store whose source register is rewritten in front of the restore is not moved -- the finding stays, which fails the build."""
-  import sys
-  sys.path.insert(0, os.path.join(ROOT, 'profiles', 'tools'))
-  import exec_join_check as CK, exec_join_patch as P
+  from dgpmp2_amd._build import exec_join_check as CK, exec_join_patch as P
   asm = '''
 _Z2k1v:
 	s_and_saveexec_b64 s[0:1], vcc
@@ -257,13 +271,12 @@ def test_exec_join_repair_on_the_compilers_own_output(tmp_path):
   """Round 6: the llc-only reproducer (profiles/r06_exec_join_repro: the optimised IR of gn_kernel<2,16,2,float,STEP,general>) through the installed llc -- the checker finds the
   misplaced spill copies of profiles/r06_compiler_fault.md in the compiler's own output, the patch moves them behind the exec restore, and the patched text still assembles.
   Skipped where llc is absent or no longer shows the signature (a fixed compiler)."""
-  import gzip, subprocess, sys
+  import gzip, subprocess
   llvm = os.environ.get('LLVM_BIN', '/opt/rocm/lib/llvm/bin')
   llc, clang = os.path.join(llvm, 'llc'), os.path.join(llvm, 'clang')
   irgz = os.path.join(ROOT, 'profiles', 'r06_exec_join_repro', 'gn_kernel_2_16_2_float_step_general.ll.gz')
   if not (os.path.exists(llc) and os.path.exists(clang)): pytest.skip('no llc / clang under %s' % llvm)
-  sys.path.insert(0, os.path.join(ROOT, 'profiles', 'tools'))
-  import exec_join_check as CK, exec_join_patch as P
+  from dgpmp2_amd._build import exec_join_check as CK, exec_join_patch as P
   ir, raw, fixed = str(tmp_path / 'one.ll'), str(tmp_path / 'one.s'), str(tmp_path / 'one_fixed.s')
   open(ir, 'wb').write(gzip.open(irgz).read())
   subprocess.check_call([llc, '-mtriple=amdgcn-amd-amdhsa', '-mcpu=gfx950', '-O3', ir, '-o', raw])
