@@ -19,7 +19,11 @@ DGP_FLAG_NONHOLONOMIC, DGP_FLAG_VEL_LIMITS = 1, 2
 DGP_QC_STATIC, DGP_QC_PERSTATE, DGP_QC_QFULL, DGP_QC_SCALAR = 0, 1, 2, 3
 DGP_SDF_ROWMAJOR, DGP_SDF_TILED4 = 0, 1
 DGP_GSDF_DENSE, DGP_GSDF_DENSE_F64, DGP_GSDF_SPARSE = 0, 1, 2
-DGP_ABI_VERSION = 6
+DGP_ABI_VERSION = 7
+# columns of dgp_traj_metrics' (B, DGP_METRIC_COUNT) float64 array, in the header's order (DGP_METRIC_*)
+METRIC_NAMES = ('avg_vel', 'avg_acc', 'avg_jerk', 'gp_mse', 'in_coll', 'num_penetrating', 'avg_penetration', 'max_penetration', 'coll_intensity',
+                'constraint_violation', 'pos_mse', 'vel_mse', 'traj_mse')
+DGP_METRIC_COUNT = len(METRIC_NAMES)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DGP_LIB_PATH') or os.path.join(_HERE, 'lib', 'libdgpmp2_hip.so')   # override: tuning builds only
@@ -54,7 +58,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -102,6 +106,11 @@ class CApi(object):
     self.sdf_2d_workspace_bytes.argtypes = [i32, i32, i32, i32]
     self.sdf_2d = f('sdf_2d'); self.sdf_2d.restype = C.c_int
     self.sdf_2d.argtypes = [vp, i32, i32, i32, i32, i32, dbl, vp, i32, i32, vp, C.c_size_t, vp]
+    # dgp_traj_metrics: bound only where the library exports it -- tests/emul's CPU emulator (prefix `emul_`) has no twin of the metrics kernel; None otherwise
+    self.traj_metrics = getattr(self.lib, prefix + 'traj_metrics', None)
+    if self.traj_metrics is not None:
+      self.traj_metrics.restype = C.c_int
+      self.traj_metrics.argtypes = [vp, i32, vp, C.POINTER(DgpSdf), dbl, vp, vp, vp, vp]
     self.time_next_launch = f('time_next_launch'); self.time_next_launch.restype = C.c_int; self.time_next_launch.argtypes = [vp, vp]
     self.event_create = f('event_create'); self.event_create.restype = C.c_int; self.event_create.argtypes = [C.POINTER(vp)]
     self.event_destroy = f('event_destroy'); self.event_destroy.restype = None; self.event_destroy.argtypes = [vp]
@@ -160,7 +169,7 @@ import sysconfig
 # never loaded by mistake
 PYCALL_PATH = os.path.join(_HERE, 'lib', '_dgp_pycall' + (sysconfig.get_config_var('EXT_SUFFIX') or '.so'))
 _PYCALL_ENTRIES = ('gn_step', 'gn_solve', 'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward',
-                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward')
+                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'traj_metrics')
 
 
 def get_api():
@@ -205,6 +214,10 @@ class CtypesPycall(object):
   def sum_partial_grids(self, *a): return self.api.sum_partial_grids(*a)
   def square_covariances(self, *a): return self.api.square_covariances(*a)
   def square_covariances_backward(self, *a): return self.api.square_covariances_backward(*a)
+
+  def traj_metrics(self, *a):
+    # (handle, batch, th, the seven DgpSdf fields, metric_eps, th_opt, metrics, obs_error, stream)
+    return self.api.traj_metrics(a[0], a[1], a[2], self._sdf(a, 3), *a[10:])
 
 
 def get_pycall():
@@ -336,6 +349,12 @@ class Solver(object):
     self.api.check(self.api.gn_step_errors_backward(self.handle, batch, th, start, goal, C.byref(sdf), C.byref(covs) if covs is not None else None,
                                                     dtheta, g_dtheta, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start, g_goal, g_sdf,
                                                     int(g_sdf_batch_stride), int(g_sdf_copies), g_qc_inv, g_obs_w, g_eps, workspace, stream))
+
+  def traj_metrics(self, batch, th, sdf, metric_eps=0.0, th_opt=None, metrics=None, obs_error=None, stream=None):
+    """dgp_traj_metrics: metrics (B, DGP_METRIC_COUNT) float64 and / or obs_error (B, n) of the I/O type, one launch."""
+    if self.api.traj_metrics is None:
+      raise NotImplementedError('%s does not export %straj_metrics (the CPU emulator has no twin of the metrics kernel)' % (self.api.path, self.api.prefix))
+    self.api.check(self.api.traj_metrics(self.handle, batch, th, C.byref(sdf), float(metric_eps), th_opt, metrics, obs_error, stream))
 
   def eval_errors_backward(self, batch, th, start, goal, sdf, covs, g_err_ext=None, g_unw_sg=None, g_unw_gp=None, g_unw_obs=None,
                            g_th=None, g_start=None, g_goal=None, g_sdf=None, g_sdf_batch_stride=0, g_eps=None, stream=None, g_sdf_copies=1):

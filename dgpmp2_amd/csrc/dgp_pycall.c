@@ -38,6 +38,8 @@ typedef int (*gn_step_errors_backward_fn)(const DgpHandle*, int32_t, const void*
 
 typedef int (*square_covs_fn)(const void*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, void*, void*, void*, void*, void*);
 typedef int (*square_covs_bwd_fn)(const void*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, const void*, const void*, const void*, void*, void*);
+typedef int (*traj_metrics_fn)(const DgpHandle*, int32_t, const void*, const DgpSdf*, double, const void*, double*, void*, void*);
+static traj_metrics_fn f_traj_metrics;
 static square_covs_fn f_square_covs;
 static square_covs_bwd_fn f_square_covs_bwd;
 typedef int (*sum_partial_grids_fn)(const void*, int32_t, int32_t, int64_t, double, void*, int32_t, void*);
@@ -87,7 +89,7 @@ static inline int64_t as_i64(PyObject* o, int* bad) {
   const DgpSdf* sdfp = sdf.data ? &sdf : NULL
 
 static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
-  NEED(12, "bind");
+  NEED(13, "bind");
   f_gn_step = (gn_step_fn)P(0);
   f_gn_solve = (gn_solve_fn)P(1);
   f_eval_errors = (eval_errors_fn)P(2);
@@ -100,6 +102,7 @@ static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
   f_sum_partial_grids = (sum_partial_grids_fn)P(9);
   f_square_covs = (square_covs_fn)P(10);
   f_square_covs_bwd = (square_covs_bwd_fn)P(11);
+  f_traj_metrics = (traj_metrics_fn)P(12);
   if (bad) return NULL;
   Py_RETURN_NONE;
 }
@@ -269,9 +272,25 @@ static PyObject* py_square_covs_bwd(PyObject* self, PyObject* const* a, Py_ssize
   return PyLong_FromLong(f_square_covs_bwd(raw, dt, B, W, ngp, n, le, dof, gq, gw, ge, graw, stream));
 }
 
+/* traj_metrics(handle, batch, th, sdf_data, sdf_rows, sdf_cols, sdf_batch_stride, sdf_layout, sdf_grad_mode, sdf_grad_indices, metric_eps, th_opt, metrics, obs_error, stream) */
+static PyObject* py_traj_metrics(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
+  NEED(15, "traj_metrics");
+  BOUND(f_traj_metrics);
+  const DgpHandle* h = (const DgpHandle*)P(0);
+  const int32_t batch = (int32_t)I(1);
+  const void* th = P(2);
+  DgpSdf sdf = {P(3), (int32_t)I(4), (int32_t)I(5), I(6), (int32_t)I(7), (int32_t)I(8), (int64_t*)P(9)};
+  const double eps = PyFloat_AsDouble(a[10]);
+  if (eps == -1.0 && PyErr_Occurred()) return NULL;
+  const void* th_opt = P(11);
+  void *metrics = P(12), *obs_error = P(13), *stream = P(14);
+  if (bad) return NULL;
+  return PyLong_FromLong(f_traj_metrics(h, batch, th, sdf.data ? &sdf : NULL, eps, th_opt, (double*)metrics, obs_error, stream));
+}
+
 static PyMethodDef methods[] = {
     {"bind", (PyCFunction)(void (*)(void))py_bind, METH_FASTCALL,
-     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward): "
+     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward, traj_metrics): "
      "addresses of the C-ABI entry points"},
     {"gn_solve_traced", (PyCFunction)(void (*)(void))py_gn_solve_traced, METH_FASTCALL, "dgp_gn_solve_traced"},
     {"gn_solve_backward", (PyCFunction)(void (*)(void))py_gn_solve_backward, METH_FASTCALL, "dgp_gn_solve_backward"},
@@ -280,6 +299,7 @@ static PyMethodDef methods[] = {
     {"sum_partial_grids", (PyCFunction)(void (*)(void))py_sum_partial_grids, METH_FASTCALL, "dgp_sum_partial_grids"},
     {"square_covariances", (PyCFunction)(void (*)(void))py_square_covs, METH_FASTCALL, "dgp_square_covariances"},
     {"square_covariances_backward", (PyCFunction)(void (*)(void))py_square_covs_bwd, METH_FASTCALL, "dgp_square_covariances_backward"},
+    {"traj_metrics", (PyCFunction)(void (*)(void))py_traj_metrics, METH_FASTCALL, "dgp_traj_metrics"},
     {"gn_step", (PyCFunction)(void (*)(void))py_gn_step, METH_FASTCALL, "dgp_gn_step"},
     {"gn_solve", (PyCFunction)(void (*)(void))py_gn_solve, METH_FASTCALL, "dgp_gn_solve"},
     {"eval_errors", (PyCFunction)(void (*)(void))py_eval_errors, METH_FASTCALL, "dgp_eval_errors"},

@@ -483,6 +483,13 @@ class DiffGPMP2Planner(nn.Module):
     """diff_gpmp2_planner.py:229-237 -> (err_sg, err_gp, err_obs), each (B,1,1)."""
     return self.plan_layer.unweighted_errors(thb, sdfb)
 
+  def trajectory_metrics(self, thb, sdfb, th_optb=None, eps=0.0, return_obs_error=False):
+    """The metrics block of the reference's validation loop (learning/test_planner.py:299-334) for the whole batch in one launch: -> plan_layer.TrajectoryMetrics
+    with (B,) device tensors in_collision (bool), coll_intensity, max_penetration, avg_penetration, gp_mse, avg_vel, avg_acc, avg_jerk, constraint_violation,
+    num_penetrating (int), pos_mse / vel_mse / traj_mse against th_optb, `.raw` (B, 13) float64 and `.obs_error` (B, n) when asked for.  `eps`: the epsilon of the
+    metrics obstacle factor (the reference uses 0.0).  No autograd; usable inside graphed_iteration / torch.cuda.graph."""
+    return self.plan_layer.trajectory_metrics(thb, sdfb, th_optb, eps, return_obs_error)
+
   def get_covariances(self, out, mode='diag_identity', learn_eps=False):
     """Learn-module output (B,1,out_dim) -> covariance tensors (diff_gpmp2_planner.py:247-290).
     fix_dynamics: obscov[, eps];  diag_identity: q^2 I;  qc_full: q q^T (dof);  q_full: q q^T (state_dim);  'diag' raises."""

@@ -1145,5 +1145,61 @@ class PlanLayer(nn.Module):
     o = self._eval_diff(thb, sdfb, st, go, eps)
     return o[1].reshape(thb.shape[0], 1), o[2], o[3]
 
+  def trajectory_metrics(self, thb, sdfb, th_optb=None, eps=0.0, return_obs_error=False):
+    """The validation metrics of every trajectory of the batch in ONE launch (dgp_traj_metrics): what learning/test_planner.py:299-334 computes per trajectory with
+    gpfactor.get_error, obsfactor.get_error, smoothness_metrics, collision_metrics, the velocity-limit loop and three MSELoss calls.  thb (B,n,d), sdfb as for
+    forward() (row-major, TiledSdf, expand()ed shared grids), th_optb (B,n,d) the expert trajectories or None, eps the epsilon of the METRICS obstacle factor (the
+    reference builds it with 0.0, not obs_params['epsilon_dist']).  No autograd: inputs are detached.  -> TrajectoryMetrics."""
+    if thb.dim() != 3 or thb.shape[1] != self.num_traj_states or thb.shape[2] != self.state_dim:
+      raise ValueError('thb must be (B,%d,%d), got %s' % (self.num_traj_states, self.state_dim, tuple(thb.shape)))
+    if sdfb is None: raise ValueError('trajectory_metrics needs the signed-distance grids (sdfb)')
+    B, dtype = thb.shape[0], thb.dtype
+    solver = self._solvers.get(dtype) or self._solver(dtype)
+    dev = thb.get_device()
+    if dev < 0: _require_cuda(thb, 'thb')
+    if self.auto_tile: sdfb = self._auto_tiled(sdfb, B)
+    sd = self._sdf_args(sdfb, dtype, B, dev)
+    thc = thb.detach().contiguous()
+    opt = None
+    if th_optb is not None:
+      if th_optb.shape != thb.shape: raise ValueError('th_optb must have the shape of thb %s, got %s' % (tuple(thb.shape), tuple(th_optb.shape)))
+      if th_optb.dtype != dtype: raise TypeError('th_optb must have the dtype of thb (%s), got %s' % (dtype, th_optb.dtype))
+      if th_optb.get_device() != dev: _same_device(dev, th_optb=th_optb)
+      opt = th_optb.detach().contiguous()
+    raw = torch.empty((B, _capi.DGP_METRIC_COUNT), dtype=torch.float64, device=thc.device)
+    oerr = torch.empty((B, self.num_traj_states), dtype=dtype, device=thc.device) if return_obs_error else None
+    _launch(dev, self._pc.traj_metrics, solver.h, B, thc.data_ptr(), *sd[:7], float(eps), _ptr(opt), raw.data_ptr(), _ptr(oerr), _raw_stream(dev))
+    return TrajectoryMetrics(raw, oerr)
+
+
+class TrajectoryMetrics(object):
+  """Result of PlanLayer.trajectory_metrics: `raw` is the (B, DGP_METRIC_COUNT) float64 device tensor dgp_traj_metrics wrote (columns _capi.METRIC_NAMES),
+  `obs_error` the (B, n) raw hinge errors or None.  The attributes named as in the reference's results file (in_collision, coll_intensity, max_penetration,
+  avg_penetration, gp_mse, avg_vel, avg_acc, avg_jerk, constraint_violation; plus num_penetrating, pos_mse, vel_mse, traj_mse) are (B,) device tensors: views of `raw`,
+  except in_collision (bool) and num_penetrating (int64), which are formed on access by one small torch op each."""
+  __slots__ = ('raw', 'obs_error')
+  _COL = {name: i for i, name in enumerate(_capi.METRIC_NAMES)}
+
+  def __init__(self, raw, obs_error=None):
+    self.raw, self.obs_error = raw, obs_error
+
+  def __getattr__(self, name):
+    if name == 'in_collision': return self.raw[:, self._COL['in_coll']] != 0
+    if name == 'num_penetrating': return self.raw[:, self._COL['num_penetrating']].to(torch.int64)
+    i = self._COL.get(name)
+    if i is None or name == 'in_coll': raise AttributeError(name)
+    return self.raw[:, i]
+
+  def keys(self):
+    return ('in_collision', 'coll_intensity', 'max_penetration', 'avg_penetration', 'gp_mse', 'avg_vel', 'avg_acc', 'avg_jerk', 'constraint_violation',
+            'num_penetrating', 'pos_mse', 'vel_mse', 'traj_mse')
+
+  def __getitem__(self, name):
+    try: return getattr(self, name)
+    except AttributeError: raise KeyError(name)
+
+  def as_dict(self):
+    return {k: getattr(self, k) for k in self.keys()}
+
 
 _NO_SDF = (None, 2, 2, 0, 0, 0, None, None)       # the seven fields of DgpSdf + the keep-alive slot

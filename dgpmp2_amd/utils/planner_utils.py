@@ -1,6 +1,8 @@
 """Callers' helpers of the planner API, restated for torch tensors on any device.
 Reference: diff_gpmp2/utils/planner_utils.py (check_convergence :3-16, check_convergence_batch :18-36,
-straight_line_traj :38-45, straight_line_trajb :47-56)."""
+straight_line_traj :38-45, straight_line_trajb :47-56, path_to_traj_avg_vel :60-71, smoothness_metrics :75-90,
+collision_metrics :92-102).  The two metrics functions score ONE trajectory on the host side, like the reference; DiffGPMP2Planner.trajectory_metrics
+scores a whole batch in one launch (dgp_traj_metrics) with the same definitions."""
 import torch
 
 
@@ -47,3 +49,37 @@ def straight_line_trajb(start_confb, goal_confb, traj_time, num_steps, dof, devi
   pos = s.unsqueeze(1) * (num_steps - i) * 1.0 / num_steps * 1.0 + g.unsqueeze(1) * i * 1.0 / num_steps * 1.0
   vel = ((goal_confb.to(dev) - start_confb.to(dev)) / traj_time * 1.0)[:, :, 0:dof].expand(B, num_steps + 1, dof)
   return torch.cat((pos, vel), dim=-1).contiguous()
+
+
+def path_to_traj_avg_vel(path, traj_time, dof, device=None):
+  """A list of len(path) configurations -> (len(path), 2*dof): the path's positions, every velocity the average velocity
+  (path[-1] - path[0]) / traj_time.  As the reference, the result is torch.zeros' default dtype."""
+  num_steps = len(path)
+  path = torch.stack([torch.as_tensor(q) for q in path])
+  th_init = torch.zeros((num_steps, 2 * dof), device=device if device is not None else torch.device('cpu'))
+  avg_vel = (path[-1] - path[0]) / traj_time * 1.0
+  th_init[:, 0:dof] = path[:, 0:dof]
+  th_init[:, dof:] = avg_vel
+  return th_init
+
+
+def smoothness_metrics(traj, total_time_sec, total_time_step):
+  """traj (n, d) -> (avg_vel, avg_acc, avg_jerk), 0-d tensors: means of the row 2-norms of traj[:, 2:], of its first differences / total_time_step
+  and of its second differences / total_time_step^2.  As in the reference the slice is 2: whatever dof (d = 6: theta, vx, vy, omega) and the divisor is
+  the step COUNT, not dt; total_time_sec is unused."""
+  tail = traj[:, 2:]
+  d1 = tail[1:] - tail[:-1]
+  d2 = d1[1:] - d1[:-1]
+  mean_row_norm = lambda rows: torch.mean(torch.norm(rows, p=2, dim=1))
+  return mean_row_norm(tail), mean_row_norm(d1 / total_time_step * 1.0), mean_row_norm(d2 / (total_time_step ** 2.0))
+
+
+def collision_metrics(traj, obs_error, total_time_sec, total_time_step):
+  """obs_error: the raw obstacle-factor errors of ONE trajectory, first dimension = state -> (in_coll, avg_penetration, max_penetration, coll_intensity) over
+  the interior states (first and last dropped).  num_penetrating = numel(nonzero(obs_error)) / 2 as in the reference: with the (n,1,1) tensor the reference's
+  callers pass (obs_error[0] of ObstacleFactor.get_error) nonzero() has three columns and this is 1.5 x the number of penetrating states -- coll_intensity
+  inherits the factor; with an (n,1) tensor it is the count itself.  in_coll is a Python bool, coll_intensity a Python float (torch.numel returns an int)."""
+  interior = obs_error[1:-1]
+  num_penetrating = torch.nonzero(interior).numel() / 2
+  step_sec = total_time_sec * 1.0 / total_time_step * 1.0
+  return num_penetrating > 0, interior.mean(), interior.max(), (num_penetrating * step_sec) / total_time_sec * 1.0

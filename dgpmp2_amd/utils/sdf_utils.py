@@ -174,6 +174,11 @@ def costmap_2d(sdf, eps):
   return (sdf <= eps).to(sdf.dtype) * (-1.0 * sdf + eps)
 
 
+def safe_sdf(sdf, eps):
+  """eps - sdf (utils/sdf_utils.py:33-35): the un-hinged obstacle loss of every cell."""
+  return -1.0 * sdf + eps
+
+
 def circles_sdf(G, circles, x_lims=(-5.0, 5.0), y_lims=(-5.0, 5.0)):
   """Synthetic SDF of SURVEY 8(d): analytic union of circles on a GxG grid, row 0 = y_max, col 0 = x_min (linspace
   endpoints), sdf = min_k(|p - c_k| - r_k), fp64."""

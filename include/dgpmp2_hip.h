@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DGP_ABI_VERSION 6
+#define DGP_ABI_VERSION 7
 
 /* status codes */
 #define DGP_OK              0
@@ -307,6 +307,46 @@ int dgp_square_covariances_backward(const void* raw, int32_t dtype, int32_t batc
 size_t dgp_sdf_2d_workspace_bytes(int32_t batch, int32_t rows, int32_t cols, int32_t padlen);
 int dgp_sdf_2d(const void* image, int32_t image_dtype, int32_t batch, int32_t rows, int32_t cols, int32_t padlen, double res,
                void* sdf_out, int32_t out_dtype, int32_t out_layout, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Validation metrics of a batch of planned trajectories in ONE launch: what the reference's validation loop computes per trajectory with some thirty small torch
+ * kernels and a nonzero() (a device -> host synchronisation) -- learning/test_planner.py:299-334, datasets/test_dataset_sensitivity.py:175-206:
+ *   smoothness_metrics / collision_metrics (utils/planner_utils.py:75-102), the raw GP and obstacle factor errors (gpfactor.get_error, gp_factor.py; obsfactor.get_error,
+ *   obstacle_factor.py:35-40 -> obstacle_cost.py:29-38), the velocity-limit count (test_planner.py:310-322) and the MSELoss against the expert trajectory (:342-344).
+ * th (B,n,d) and th_opt (B,n,d; optional) in the handle's io_dtype; sdf as for dgp_gn_step (row-major or DGP_SDF_TILED4, shared or per sample).
+ * metric_eps: the epsilon of the METRICS obstacle factor, which the reference builds with eps = 0.0 and NOT with obs_params['epsilon_dist'] (test_planner.py:140,182-184):
+ *   a state has a hinge error where dist <= metric_eps + sphere_radius, exactly where the step kernels give it one at that epsilon.  Negative values are allowed.
+ * Outputs (either may be NULL, not both):
+ *   metrics   (B, DGP_METRIC_COUNT) DOUBLES whatever io_dtype, columns DGP_METRIC_* below; needs num_states >= 3 (DGP_EINVAL otherwise: no interior state -- the reference
+ *             raises on the max of an empty tensor there)
+ *   obs_error (B, n) io_dtype: the raw hinge error of every state, obs_error[0][:, 0, 0] of the reference
+ * The definitions are the reference's, quirks included (tests/golden/g9_metrics.npz pins them):
+ *   AVG_VEL / AVG_ACC / AVG_JERK  means of the row 2-norms of traj[:, 2:], (traj[1:] - traj[:-1])[:, 2:] / total_time_step and the second differences [:, 2:] /
+ *             total_time_step^2 over n, n - 1 and n - 2 rows: columns 2.. whatever dof (d = 6: theta, vx, vy, omega), divided by the STEP COUNT n - 1, not by dt
+ *   GP_MSE    mean of e^2 over the (n - 1) d entries of e_i = x_{i+1} - Phi x_i  (torch.mean(torch.sum(gp_error ** 2, dim=-1)), gp_error (1, n-1, d, 1))
+ *   IN_COLL, NUM_PENETRATING, AVG_PENETRATION, MAX_PENETRATION, COLL_INTENSITY  over the n - 2 INTERIOR states (the first and the last are dropped).  The reference
+ *             calls collision_metrics with obs_error[0] of shape (n,1,1): nonzero() returns three columns and its `num_penetrating = numel / 2` is 1.5 x the number of
+ *             penetrating states.  NUM_PENETRATING here is the plain count of interior states with a non-zero hinge error; COLL_INTENSITY = (1.5 count dt) / total_time_sec
+ *             EQUALS the reference's value as called from test_planner.py:304 (the factor 1.5 included); IN_COLL = count > 0 as 0.0 / 1.0
+ *   CONSTRAINT_VIOLATION  fraction of ALL n states with |th[2]| > v_x or |th[3]| > v_y (columns 2 and 3 whatever dof); 0 unless the handle has DGP_FLAG_VEL_LIMITS
+ *   POS_MSE / VEL_MSE / TRAJ_MSE  MSELoss (mean) of th against th_opt over columns [0, dof), [dof, d) and all; 0 when th_opt is NULL
+ * Arithmetic in fp64; the sums, maxima and counts of a trajectory are reduced inside its wavefront in a fixed order (no atomics): results are bit-identical from run to
+ * run, for either grid layout and wherever the trajectory sits in the batch.  One launch, nothing allocated or synchronised: capturable in a HIP graph. */
+#define DGP_METRIC_AVG_VEL               0
+#define DGP_METRIC_AVG_ACC               1
+#define DGP_METRIC_AVG_JERK              2
+#define DGP_METRIC_GP_MSE                3
+#define DGP_METRIC_IN_COLL               4
+#define DGP_METRIC_NUM_PENETRATING       5
+#define DGP_METRIC_AVG_PENETRATION       6
+#define DGP_METRIC_MAX_PENETRATION       7
+#define DGP_METRIC_COLL_INTENSITY        8
+#define DGP_METRIC_CONSTRAINT_VIOLATION  9
+#define DGP_METRIC_POS_MSE              10
+#define DGP_METRIC_VEL_MSE              11
+#define DGP_METRIC_TRAJ_MSE             12
+#define DGP_METRIC_COUNT                13
+int dgp_traj_metrics(const DgpHandle* h, int32_t batch, const void* th, const DgpSdf* sdf, double metric_eps, const void* th_opt,
+                     double* metrics, void* obs_error, void* stream);
 
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
