@@ -47,7 +47,7 @@ inline int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// Shapes the kernels are instantiated for (see DGP_FOR_EACH_SHAPE in dgpmp2_hip.hip): LPT in {16,32,64} x C in {1,2,4}.
+// Shapes the kernels are instantiated for (with_kernel_args below): LPT in {16,32,64} x C in {1,2,4}.
 constexpr int kMaxStates = 256;
 // Longer trajectories run the loop kernels of gn_long.h (one trajectory per wavefront, ceil(n / 64) rows per lane), whose limit is the
 // wavefront's LDS block of (rows per lane - 1) parked (S_k^-1, z_k) slots: 16 rows per lane for d = 4 (105 KB), 10 for d = 6 (127 KB = dgp::long_lds_bytes<6>(640)).
@@ -74,7 +74,7 @@ inline bool shape_supported(int lpt, int c) { return (lpt == 16 || lpt == 32 || 
 enum { FAM_STATIC = 0, FAM_GENERAL = 1, FAM_KRON_BWD = 2 };
 // `tiled` (DgpSdf::layout = DGP_SDF_TILED4, and the step kernels with the errors epilogue): the twin translation units hold the shapes (16,4) and (32,4) only
 // (num_states <= 128, host-checked)
-inline bool tiled_shape_ok(int lpt, int c) { return c == 4 && (lpt == 16 || lpt == 32); }
+constexpr bool tiled_shape_ok(int lpt, int c) { return c == 4 && (lpt == 16 || lpt == 32); }
 constexpr int kMaxStatesTiled = 128;
 inline DgpShape choose_shape(const DgpHandle* h, int B, int family = FAM_STATIC, bool tiled = false) {
   const bool general = family == FAM_GENERAL;
@@ -101,23 +101,163 @@ inline DgpShape choose_shape(const DgpHandle* h, int B, int family = FAM_STATIC,
   return best;
 }
 
-// kernel family of a launch for the shape choice (mode: dgp::MODE_* or 3 = backward)
-inline int shape_family(int mode, const dgp::GnParams& p) {
-  if (mode == dgp::MODE_EVAL) return FAM_STATIC;
-  const int qk = dgp::kernel_variant(p);
-  if (qk == dgp::QK_GENERAL) return FAM_GENERAL;
-  if (qk == dgp::QK_KRON && mode == 3) return FAM_KRON_BWD;
-  return FAM_STATIC;
+// ---- which kernel a launch runs: decided HERE, for the product's launchers (gn_device.h) and the test emulator (tests/emul) alike ----------------------
+// Mode of a launch: the kernel modes of gn_lane.h, the backward kernels, and the two launches that resolve to one of those on other kernels.
+enum { MODE_STEP = dgp::MODE_STEP, MODE_SOLVE = dgp::MODE_SOLVE, MODE_EVAL = dgp::MODE_EVAL, MODE_BACKWARD = 3,
+       MODE_CHAIN = 4,           // dgp_gn_solve_backward: MODE_BACKWARD on the chain kernels (static covariances)
+       MODE_STEP_ERRS = 5 };     // dgp_gn_step_errors in one launch: MODE_STEP on the twin kernels that carry the errors epilogue (gn_lane.h: DGP_STEP_ERRS)
+// kernel family of a launch for the shape choice (mode: the kernel's, MODE_STEP ... MODE_BACKWARD; qk: dgp::kernel_variant): the error kernel is timed like the static ones
+constexpr int shape_family(int mode, int qk) {
+  return mode == MODE_EVAL ? FAM_STATIC : (qk == dgp::QK_GENERAL ? FAM_GENERAL : ((qk == dgp::QK_KRON && mode == MODE_BACKWARD) ? FAM_KRON_BWD : FAM_STATIC));
+}
+// The two names tests/emul/emul_main.cpp took from this header before choose_kernel, kept so that the emulator source of the commit before this one still
+// compiles against this header (that commit's tests then run against this library).  Nothing in the tree uses them.
+enum { kModeStepErrs = MODE_STEP_ERRS };
+inline int shape_family(int mode, const dgp::GnParams& p) { return shape_family(mode, dgp::kernel_variant(p)); }
+// Unit family: the three builds of gn_inst.hip (dgpmp2_amd/_build/units.py) -- the standard kernels, their twins for 4 x 4-tiled grids (-DDGP_TL=1) and the step
+// kernels with the errors epilogue (-DDGP_STEP_ERRS=1); the values are those of the kernels' trailing template argument, DGP_TL + 2 * DGP_STEP_ERRS.
+enum { UNIT_STANDARD = 0, UNIT_TILED = 1, UNIT_STEP_ERRS = 2, NUM_UNITS = 3, UNIT_ANY = NUM_UNITS };
+// Group: the kernels of one unit family, robot and I/O type are spread over translation units so that they build in parallel.
+enum { GROUP_NONE = -1, GROUP_STATIC = 0, GROUP_GENERIC = 1, GROUP_BACKWARD = 2, GROUP_KRON = 3, GROUP_CHAIN = 4, NUM_GROUPS = 5, GROUP_ANY = NUM_GROUPS };
+
+// THE list of kernels: the group that holds kernel (mode, qk, chain) -- mode: MODE_STEP / SOLVE / EVAL (gn_kernel) or MODE_BACKWARD (gn_backward_kernel), qk: dgp::QK_* --,
+// GROUP_NONE where there is no such kernel.
+constexpr int kernel_group(int mode, int qk, bool chain) {
+  if (chain) return (mode == MODE_BACKWARD && (qk == dgp::QK_GENERAL || qk == dgp::QK_STATIC || dgp::is_wb(qk))) ? GROUP_CHAIN : GROUP_NONE;      // (static covariances: no covariance gradient)
+  if (mode == MODE_EVAL) return qk == dgp::QK_GENERAL ? GROUP_GENERIC : GROUP_NONE;      // (one error kernel, whatever the covariances)
+  if (qk == dgp::QK_KRON) return GROUP_KRON;                                              // everything for per-state Q_c^-1 tensors: STEP, SOLVE, backward
+  if (mode == MODE_BACKWARD) return GROUP_BACKWARD;
+  if (qk == dgp::QK_SCALED) return mode == MODE_STEP ? GROUP_STATIC : GROUP_NONE;         // (no fused loop for DGP_QC_SCALAR)
+  return qk == dgp::QK_GENERAL ? GROUP_GENERIC : GROUP_STATIC;
+}
+// ... and where each is built: the Woodbury kernels at four states per lane, the twin units at their two shapes, the step-errors twins for MODE_STEP only
+// (UNIT_ANY / GROUP_ANY: everything -- the emulator)
+constexpr bool kernel_built(int unit, int group, int lpt, int c, int mode, int qk, bool chain) {
+  const int grp = kernel_group(mode, qk, chain);
+  return grp != GROUP_NONE && (group == GROUP_ANY || group == grp) && (c == 4 || !dgp::is_wb(qk)) &&
+         (unit == UNIT_ANY || unit == UNIT_STANDARD || tiled_shape_ok(lpt, c)) && (unit != UNIT_STEP_ERRS || mode == MODE_STEP);
 }
 
-// dgp_step_kernel_variant: the dgp::QK_* variant a static-covariance step of this batch size launches (mirrors launch_typed)
-inline int step_kernel_variant(const DgpHandle* h, int B) {
+// dgp_gn_step_errors as ONE launch: where the step kernels with the errors epilogue exist (round 5) -- row-major grid, up to 128 states (the two four-states-per-lane
+// shapes), no forced shape; d = 4: every covariance representation, d = 6: everything but the general family (q_full / a non-diagonal Q_c_inv: those twins were built and
+// measured in round 6 -- exact, but 92 us against 66 + 8 us for the two launches, profiles/r06_d6_general_twin.txt: not shipped).  (Round 5 excluded two more twins --
+// <3,16,4,float,STEP,static> and <2,32,4,float,STEP,general> -- after wrong results on the GPU: the exec-join miscompile of profiles/r06_compiler_fault.md, which the
+// build repairs since round 6; profiles/tools/r06_twin_hooks.patch brings the exclusion back for the reproducer.)
+inline bool step_errs_twin_ok(const DgpHandle* h, const dgp::GnParams& p) {
+  return p.sdf_layout == 0 && p.n <= kMaxStatesTiled && !h->force_lpt && !(h->cfg.dof == 3 && dgp::kernel_variant(p) == dgp::QK_GENERAL);
+}
+
+struct KernelChoice {
+  int unit, group;      // UNIT_*, GROUP_*: the translation unit that holds the kernel (group: GROUP_NONE for a long launch)
+  int mode, qk;         // the kernel's MODE (MODE_STEP ... MODE_BACKWARD) and covariance variant (dgp::QK_*, the Woodbury variants resolved)
+  bool chain;           // the chain backward kernels
+  bool is_long;         // n > 256: the loop kernels of gn_long.h (mode only; sh reports the rows per lane)
+  DgpShape sh;
+};
+
+// The kernel launch `mode` (MODE_*) of the filled arguments p runs; DGP_OK or an error.  Branches only: this runs in front of every launch.
+inline int choose_kernel(const DgpHandle* h, int mode, const dgp::GnParams& p, const char* what, KernelChoice& kc) {
+  const bool tiled = p.sdf_layout != 0 && p.sdf != nullptr;
+  if (tiled && p.n > kMaxStatesTiled)
+    return fail(DGP_EUNSUPPORTED, "%s: tiled grids (DGP_SDF_TILED4) are implemented for num_states <= %d (launch shapes (16,4) and (32,4))", what, kMaxStatesTiled);
+  if (mode == MODE_STEP_ERRS && !step_errs_twin_ok(h, p)) return fail(DGP_EINVAL, "%s: no step kernel with the errors epilogue for this call", what);
+  kc.unit = mode == MODE_STEP_ERRS ? UNIT_STEP_ERRS : (tiled ? UNIT_TILED : UNIT_STANDARD);
+  kc.chain = mode == MODE_CHAIN;
+  kc.mode = mode == MODE_STEP_ERRS ? (int)MODE_STEP : (kc.chain ? (int)MODE_BACKWARD : mode);
+  kc.is_long = is_long(p.n);
+  kc.qk = (kc.mode == MODE_EVAL || kc.is_long) ? (int)dgp::QK_GENERAL : dgp::kernel_variant(p);      // (long trajectories: generic rows, no static / Woodbury specialisation)
+  kc.sh = choose_shape(h, p.B, shape_family(kc.mode, kc.qk), kc.unit != UNIT_STANDARD);      // (a long launch has one shape: the rows per lane, which dgp_launch_shape reports)
+  if (kc.is_long) { kc.group = GROUP_NONE; return DGP_OK; }      // (no chain kernels there: fill_solve_backward refuses)
+  if (kc.qk == dgp::QK_STATIC && dgp::wb_applies(p, kc.sh.lpt, kc.sh.c)) kc.qk = p.n == kc.sh.lpt * kc.sh.c ? dgp::QK_WB : dgp::QK_WBR;      // exactly filled / ragged
+  kc.group = kernel_group(kc.mode, kc.qk, kc.chain);
+  if (kc.group == GROUP_NONE) return fail(DGP_EUNSUPPORTED, "%s: no kernel for mode %d with covariance variant %d", what, mode, kc.qk);
+  return DGP_OK;
+}
+
+// dgp_launch_shape / dgp_step_kernel_variant: what a static-covariance step of this batch size launches (per-call q_full tensors may pick another shape)
+inline int static_step_choice(const DgpHandle* h, int32_t batch, KernelChoice& kc) {
+  if (!h || batch <= 0) return fail(DGP_EINVAL, "null handle or non-positive batch");
   dgp::GnParams p = h->base;
   p.qc_mode = dgp::QC_STATIC;
-  const DgpShape sh = choose_shape(h, B);
-  if (is_long(p.n) || !dgp::use_static_kernels(p)) return dgp::QK_GENERAL;
-  if (!dgp::wb_applies(p, sh.lpt, sh.c)) return dgp::QK_STATIC;
-  return p.n == sh.lpt * sh.c ? dgp::QK_WB : dgp::QK_WBR;
+  p.B = batch;
+  return choose_kernel(h, MODE_STEP, p, "dgp_launch_shape", kc);
+}
+inline int launch_shape(const DgpHandle* h, int32_t batch, int32_t* lpt, int32_t* c) {
+  KernelChoice kc;
+  const int rc = static_step_choice(h, batch, kc);
+  if (rc != DGP_OK) return rc;
+  if (lpt) *lpt = kc.sh.lpt;
+  if (c) *c = kc.sh.c;
+  return DGP_OK;
+}
+inline int step_kernel_variant(const DgpHandle* h, int32_t batch) {
+  KernelChoice kc;
+  const int rc = static_step_choice(h, batch, kc);
+  return rc != DGP_OK ? rc : kc.qk;
+}
+
+// From a KernelChoice to the compile-time arguments of its kernel: f(KernelArgs<...>()) is called for the kernel kc names, if translation unit <UNIT, GROUP> holds it
+// (kernel_built) -> whether it does.  The launchers start the HIP kernel from it, the emulator runs the lane program.  UNIT and GROUP are part of every signature:
+// the units of one (dof, io dtype) must not share ONE weak host instantiation of these templates -- the linker would keep either, and the twin units would start
+// the standard kernels.  (The cases stand in the order the kernels have in a unit's assembly, the chain unit starting with its general kernel: a reordering
+// changes no kernel but every record that is held against the assembly.)
+template <int DOF_, int LPT_, int C_, typename IO_, int MODE_, int QK_, bool CHAIN_>
+struct KernelArgs {
+  static constexpr int DOF = DOF_, LPT = LPT_, C = C_, MODE = MODE_, QK = QK_;
+  static constexpr bool CHAIN = CHAIN_;
+  typedef IO_ IO;
+};
+template <int UNIT, int GROUP, int DOF, typename IO, int LPT, int C, int QK, int MODE, bool CHAIN, typename F>
+bool with_kernel(F& f) {
+  if constexpr (kernel_built(UNIT, GROUP, LPT, C, MODE, QK, CHAIN)) { f(KernelArgs<DOF, LPT, C, IO, MODE, QK, CHAIN>()); return true; }
+  else return false;
+}
+template <int UNIT, int GROUP, int DOF, typename IO, int LPT, int C, int QK, bool CHAIN, typename F>
+bool with_kernel_of_variant(const KernelChoice& kc, F& f) {
+  if constexpr (CHAIN) return with_kernel<UNIT, GROUP, DOF, IO, LPT, C, QK, MODE_BACKWARD, true>(f);
+  else switch (kc.mode) {
+    case MODE_STEP: return with_kernel<UNIT, GROUP, DOF, IO, LPT, C, QK, MODE_STEP, false>(f);
+    case MODE_SOLVE: return with_kernel<UNIT, GROUP, DOF, IO, LPT, C, QK, MODE_SOLVE, false>(f);
+    case MODE_EVAL: return with_kernel<UNIT, GROUP, DOF, IO, LPT, C, QK, MODE_EVAL, false>(f);
+    case MODE_BACKWARD: return with_kernel<UNIT, GROUP, DOF, IO, LPT, C, QK, MODE_BACKWARD, false>(f);
+  }
+  return false;
+}
+template <int UNIT, int GROUP, int DOF, typename IO, int LPT, int C, typename F>
+bool with_kernel_of_shape(const KernelChoice& kc, F& f) {
+  if (kc.chain) switch (kc.qk) {
+    case dgp::QK_GENERAL: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_GENERAL, true>(kc, f);
+    case dgp::QK_WB: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_WB, true>(kc, f);
+    case dgp::QK_WBR: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_WBR, true>(kc, f);
+    case dgp::QK_STATIC: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_STATIC, true>(kc, f);
+  }
+  else switch (kc.qk) {
+    case dgp::QK_SCALED: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_SCALED, false>(kc, f);
+    case dgp::QK_WB: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_WB, false>(kc, f);
+    case dgp::QK_WBR: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_WBR, false>(kc, f);
+    case dgp::QK_STATIC: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_STATIC, false>(kc, f);
+    case dgp::QK_GENERAL: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_GENERAL, false>(kc, f);
+    case dgp::QK_KRON: return with_kernel_of_variant<UNIT, GROUP, DOF, IO, LPT, C, dgp::QK_KRON, false>(kc, f);
+  }
+  return false;
+}
+template <int UNIT, int GROUP, int DOF, typename IO, int C, typename F>
+bool with_kernel_of_c(const KernelChoice& kc, F& f) {
+  switch (kc.sh.lpt) {
+    case 16: return with_kernel_of_shape<UNIT, GROUP, DOF, IO, 16, C>(kc, f);
+    case 32: return with_kernel_of_shape<UNIT, GROUP, DOF, IO, 32, C>(kc, f);
+    case 64: return with_kernel_of_shape<UNIT, GROUP, DOF, IO, 64, C>(kc, f);
+  }
+  return false;
+}
+template <int UNIT, int GROUP, int DOF, typename IO, typename F>
+bool with_kernel_args(const KernelChoice& kc, F&& f) {      // every (LPT, C) of shape_supported
+  switch (kc.sh.c) {
+    case 1: return with_kernel_of_c<UNIT, GROUP, DOF, IO, 1>(kc, f);
+    case 2: return with_kernel_of_c<UNIT, GROUP, DOF, IO, 2>(kc, f);
+    case 4: return with_kernel_of_c<UNIT, GROUP, DOF, IO, 4>(kc, f);
+  }
+  return false;
 }
 
 // The constant blocks of a GP factor under the configured (static) Q_c_inv: Q^-1 exactly as dgp::fixed_Qinv builds it,
@@ -389,8 +529,7 @@ inline int fill_solve_backward(const DgpHandle* h, int32_t batch, const void* st
 }
 
 // ---- the round-4 entry points, generic over how a kernel is launched (HIP: dgpmp2_hip.hip; the test emulator: tests/emul) ------------------
-// `launch(mode, p, g)` -> DGP_OK or an error code; mode: dgp::MODE_* / 3 = backward / 4 = chain backward.
-enum { kModeBackward = 3, kModeChain = 4, kModeStepErrs = 5 };      // kModeStepErrs: MODE_STEP on the twin kernels that carry the errors epilogue (gn_lane.h: DGP_STEP_ERRS)
+// `launch(mode, p, g)` -> DGP_OK or an error code; mode: MODE_* above.
 
 template <typename Launch>
 int gn_solve_traced(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf, const DgpCovs* covs,
@@ -402,7 +541,7 @@ int gn_solve_traced(const DgpHandle* h, int32_t batch, const void* th_init, cons
   if (th_hist && is_long(p.n)) return fail(DGP_EUNSUPPORTED, "th_hist is not implemented for num_states > 256");
   if (th_hist && !iters) return fail(DGP_EINVAL, "th_hist needs iters (rows at or past iters[b] are not written)");
   p.dtheta = th_hist;              // (the fused loop has no dtheta output: the field carries the history pointer, gn_lane.h)
-  return launch(dgp::MODE_SOLVE, p, (const dgp::GnGradParams*)nullptr);
+  return launch((int)MODE_SOLVE, p, (const dgp::GnGradParams*)nullptr);
 }
 
 template <typename Launch>
@@ -414,7 +553,7 @@ int gn_solve_backward(const DgpHandle* h, int32_t batch, const void* start, cons
   int rc = fill_solve_backward(h, batch, start, goal, sdf, max_iters, th_hist, th_out, iters, g_th_out, g_th_init, g_start, g_goal, g_sdf,
                                g_sdf_batch_stride, g_sdf_copies, p, g);
   if (rc != DGP_OK) return rc;
-  return launch((int)kModeChain, p, &g);
+  return launch((int)MODE_CHAIN, p, &g);
 }
 
 template <typename Launch>
@@ -425,22 +564,11 @@ int gn_step_errors(const DgpHandle* h, int32_t batch, const void* th, const void
   if (rc != DGP_OK) return rc;
   const bool errs = unw_sg || unw_gp || unw_obs;
   if (errs && is_long(p.n)) return fail(DGP_EUNSUPPORTED, "dgp_gn_step_errors is not implemented for num_states > 256");
-  // ONE launch where the step kernels with the errors epilogue exist (round 5): row-major grid, up to 128 states (the two four-states-per-lane shapes); d = 4: every
-  // covariance representation, d = 6: everything but the general family (q_full / a non-diagonal Q_c_inv: those twins were built and measured in round 6 -- exact, but
-  // 92 us against 66 + 8 us for the two launches, profiles/r06_d6_general_twin.txt: not shipped); everything else: the error kernel stream-ordered behind the step, as in round 4.  (Round 5 excluded two more twins -- <3,16,4,float,STEP,static> and <2,32,4,float,STEP,general> -- after wrong
-  // results on the GPU: the exec-join miscompile of profiles/r06_compiler_fault.md, which the build repairs since round 6.)
-  const int qk = dgp::kernel_variant(p);
-  const bool twin_ok = DGP_EXCLUDE_REPAIRED_TWINS ? (!(h->cfg.dof == 3 && (qk == dgp::QK_GENERAL || (qk == dgp::QK_STATIC && !p.wb_ok))) &&
-                                                     !(qk == dgp::QK_GENERAL && h->cfg.io_dtype == DGP_F32 && p.n > 64))
-                                                  : !(h->cfg.dof == 3 && qk == dgp::QK_GENERAL);
-  if (errs && p.sdf_layout == 0 && p.n <= kMaxStatesTiled && twin_ok && !h->force_lpt) {
+  if (errs && step_errs_twin_ok(h, p)) {      // ONE launch; everything else: the error kernel stream-ordered behind the step, as in round 4
     p.unw_sg = unw_sg; p.unw_gp = unw_gp; p.unw_obs = unw_obs;
-#if DGP_TWIN_REPRO      // reproducer builds (-DDGP_TWIN_REPRO=1): DGP_TWIN_NO_ERRS=1 launches the twin kernel with its epilogue switched off at run time (is the main body or the epilogue wrong?)
-    if (getenv("DGP_TWIN_NO_ERRS")) p.unw_sg = p.unw_gp = p.unw_obs = nullptr;
-#endif
-    return launch((int)kModeStepErrs, p, (const dgp::GnGradParams*)nullptr);
+    return launch((int)MODE_STEP_ERRS, p, (const dgp::GnGradParams*)nullptr);
   }
-  rc = launch(dgp::MODE_STEP, p, (const dgp::GnGradParams*)nullptr);
+  rc = launch((int)MODE_STEP, p, (const dgp::GnGradParams*)nullptr);
   if (rc != DGP_OK || !errs) return rc;
   // the unweighted errors at th + dtheta: the error kernel with dtheta as addend, stream-ordered behind the step (only eps of the covariances enters them)
   DgpCovs c = {DGP_QC_STATIC, nullptr, nullptr, covs ? covs->eps : nullptr};
@@ -448,7 +576,7 @@ int gn_step_errors(const DgpHandle* h, int32_t batch, const void* th, const void
   if (rc != DGP_OK) return rc;
   p.dtheta = dtheta;               // MODE_EVAL: the addend (gn_lane.h)
   p.vec_io = (aligned16(th) && aligned16(dtheta)) ? 1 : 0;
-  return launch(dgp::MODE_EVAL, p, (const dgp::GnGradParams*)nullptr);
+  return launch((int)MODE_EVAL, p, (const dgp::GnGradParams*)nullptr);
 }
 
 template <typename Launch>
@@ -468,7 +596,7 @@ int gn_step_errors_backward(const DgpHandle* h, int32_t batch, const void* th, c
     if (rc != DGP_OK) return rc;
     g.f_unw_sg = g_unw_sg; g.f_unw_gp = g_unw_gp; g.f_unw_obs = g_unw_obs; g.f_addend = dtheta;
     g.g_sdf_passes = 2;
-    return launch((int)kModeBackward, p, &g);
+    return launch((int)MODE_BACKWARD, p, &g);
   }
   if (errs) {
     // d = 6 (no prologue in its backward kernels: registers, LDS -- gn_backward.h) and long trajectories (the loop kernels of gn_long.h): two launches, as in round 4
@@ -481,7 +609,7 @@ int gn_step_errors_backward(const DgpHandle* h, int32_t batch, const void* th, c
     g.th_addend = dtheta;
     g.g_sdf_passes = 2; g.g_sdf_pass0 = 1;      // DGP_GSDF_SPARSE: the taps at th + dtheta are the second block
     p.vec_io = (p.vec_io && aligned16(dtheta)) ? 1 : 0;
-    rc = launch((int)kModeBackward, p, &g);
+    rc = launch((int)MODE_BACKWARD, p, &g);
     if (rc != DGP_OK) return rc;
   }
   // the step's backward (the only launch without error cotangents); behind launch 1 the workspace joins the dtheta cotangent and g_th,
@@ -493,7 +621,7 @@ int gn_step_errors_backward(const DgpHandle* h, int32_t batch, const void* th, c
     g.g_th_new = workspace; g.accumulate = 1; g.g_sdf_passes = 2;
     p.vec_io = (p.vec_io && aligned16(workspace)) ? 1 : 0;
   }
-  return launch((int)kModeBackward, p, &g);
+  return launch((int)MODE_BACKWARD, p, &g);
 }
 
 }  // namespace dgp_host

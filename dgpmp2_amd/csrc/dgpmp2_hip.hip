@@ -16,32 +16,21 @@ int drop_events(int rc) {
   return rc;
 }
 
-// status of a launch.  kTiledTooLong is this file's PRIVATE code for "tiled grid beyond what the tiled translation units hold" (see launch()): not a value the HIP
-// runtime returns, so a genuine hipErrorNotSupported of a launch is reported as what it is
-static const hipError_t kTiledTooLong = (hipError_t)0x7f5d0001;
 int hip_rc(hipError_t e, const char* what) {
   if (e == hipSuccess) return DGP_OK;
-  if (e == kTiledTooLong)
-    return fail(DGP_EUNSUPPORTED, "%s: tiled grids (DGP_SDF_TILED4) are implemented for num_states <= %d (launch shapes (16,4) and (32,4))", what, dgp_host::kMaxStatesTiled);
   return fail(DGP_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
 }
 
-hipError_t launch(const DgpHandle* h, int mode, const dgp::GnParams& p, const dgp::GnGradParams* g, hipStream_t s) {
-  const bool tiled = p.sdf_layout != 0 && p.sdf != nullptr;
-  if (tiled && p.n > dgp_host::kMaxStatesTiled) return kTiledTooLong;
-  if (mode == dgp_host::kModeStepErrs) {          // dgp_gn_step_errors as ONE launch: the step kernels with the errors epilogue (gn_inst.hip with -DDGP_STEP_ERRS=1; host-checked: available)
-    static const DgpLaunchFn etab[2][2][3] = {{{dgp_launch_2e_f32_g0, dgp_launch_2e_f32_g3, dgp_launch_2e_f32_g1}, {dgp_launch_2e_f64_g0, dgp_launch_2e_f64_g3, dgp_launch_2e_f64_g1}},
-                                             {{dgp_launch_3e_f32_g0, dgp_launch_3e_f32_g3, nullptr}, {dgp_launch_3e_f64_g0, dgp_launch_3e_f64_g3, nullptr}}};
-    const int grp = dgp_dev::launch_group(dgp::MODE_STEP, p);
-    if (tiled || (grp != dgp_dev::GROUP_STATIC && grp != dgp_dev::GROUP_KRON && grp != dgp_dev::GROUP_GENERIC)) return hipErrorInvalidValue;
-    if (grp == dgp_dev::GROUP_GENERIC && h->cfg.dof != 2) return hipErrorInvalidValue;      // (host-checked: dgp_host::gn_step_errors)
-    const DgpShape she = dgp_host::choose_shape(h, p.B, dgp_host::shape_family(dgp::MODE_STEP, p), /*four states per lane=*/true);
-    return etab[h->cfg.dof - 2][h->cfg.io_dtype == DGP_F64 ? 1 : 0][grp == dgp_dev::GROUP_KRON ? 1 : (grp == dgp_dev::GROUP_GENERIC ? 2 : 0)](she, dgp::MODE_STEP, p, g, s);
-  }
-  if (dgp_host::is_long(p.n)) return dgp_launch_long(h->cfg.dof, h->cfg.io_dtype == DGP_F64, mode, p, g, s);      // n > 256: gn_long.h
-  const DgpShape sh = dgp_host::choose_shape(h, p.B, dgp_host::shape_family(mode, p), tiled);
-  // [tiled][dof - 2][io dtype][kernel group] -> the translation unit that holds the kernel (gn_inst.hip; the tiled units: the same kernels compiled with -DDGP_TL=1)
-  static const DgpLaunchFn table[2][2][2][dgp_dev::NUM_GROUPS] = {
+// One launch of entry point `what`: dgp_host::choose_kernel says which kernel, the table which translation unit holds it.
+int launch(const DgpHandle* h, int mode, const dgp::GnParams& p, const dgp::GnGradParams* g, hipStream_t s, const char* what) {
+  dgp_host::KernelChoice kc;
+  const int rc = dgp_host::choose_kernel(h, mode, p, what, kc);
+  if (rc != DGP_OK) return drop_events(rc);
+  const int f64 = h->cfg.io_dtype == DGP_F64 ? 1 : 0;
+  if (kc.is_long) return hip_rc(dgp_launch_long(h->cfg.dof, f64 != 0, kc.mode, p, g, s), what);      // n > 256: gn_long.h
+  // [unit family][dof - 2][io dtype][kernel group] -> the launcher of the translation unit that holds the kernel (gn_inst.hip; dgpmp2_amd/_build/units.py builds exactly
+  // these); null: not built -- the step-errors twins have no backward kernels, and no general ones for d = 6
+  static DgpLaunch* const table[dgp_host::NUM_UNITS][2][2][dgp_host::NUM_GROUPS] = {
       {{{dgp_launch_2_f32_g0, dgp_launch_2_f32_g1, dgp_launch_2_f32_g2, dgp_launch_2_f32_g3, dgp_launch_2_f32_g4},
         {dgp_launch_2_f64_g0, dgp_launch_2_f64_g1, dgp_launch_2_f64_g2, dgp_launch_2_f64_g3, dgp_launch_2_f64_g4}},
        {{dgp_launch_3_f32_g0, dgp_launch_3_f32_g1, dgp_launch_3_f32_g2, dgp_launch_3_f32_g3, dgp_launch_3_f32_g4},
@@ -49,9 +38,14 @@ hipError_t launch(const DgpHandle* h, int mode, const dgp::GnParams& p, const dg
       {{{dgp_launch_2t_f32_g0, dgp_launch_2t_f32_g1, dgp_launch_2t_f32_g2, dgp_launch_2t_f32_g3, dgp_launch_2t_f32_g4},
         {dgp_launch_2t_f64_g0, dgp_launch_2t_f64_g1, dgp_launch_2t_f64_g2, dgp_launch_2t_f64_g3, dgp_launch_2t_f64_g4}},
        {{dgp_launch_3t_f32_g0, dgp_launch_3t_f32_g1, dgp_launch_3t_f32_g2, dgp_launch_3t_f32_g3, dgp_launch_3t_f32_g4},
-        {dgp_launch_3t_f64_g0, dgp_launch_3t_f64_g1, dgp_launch_3t_f64_g2, dgp_launch_3t_f64_g3, dgp_launch_3t_f64_g4}}}};
-  const int f64 = h->cfg.io_dtype == DGP_F64 ? 1 : 0;
-  return table[tiled ? 1 : 0][h->cfg.dof - 2][f64][dgp_dev::launch_group(mode, p)](sh, mode, p, g, s);
+        {dgp_launch_3t_f64_g0, dgp_launch_3t_f64_g1, dgp_launch_3t_f64_g2, dgp_launch_3t_f64_g3, dgp_launch_3t_f64_g4}}},
+      {{{dgp_launch_2e_f32_g0, dgp_launch_2e_f32_g1, nullptr, dgp_launch_2e_f32_g3, nullptr},
+        {dgp_launch_2e_f64_g0, dgp_launch_2e_f64_g1, nullptr, dgp_launch_2e_f64_g3, nullptr}},
+       {{dgp_launch_3e_f32_g0, nullptr, nullptr, dgp_launch_3e_f32_g3, nullptr},
+        {dgp_launch_3e_f64_g0, nullptr, nullptr, dgp_launch_3e_f64_g3, nullptr}}}};
+  DgpLaunch* const unit = table[kc.unit][h->cfg.dof - 2][f64][kc.group];
+  if (!unit) return drop_events(fail(DGP_EUNSUPPORTED, "%s: the kernel of this launch is not built (unit family %d, group %d)", what, kc.unit, kc.group));
+  return hip_rc(unit(kc, p, g, s), what);
 }
 
 // dgp_sum_partial_grids: out[e] = scale * sum_c partial[c][e] -- the partial copies of a shared grid's gradient (dgp_gn_step_backward's g_sdf_copies) summed and cast in
@@ -191,26 +185,15 @@ int dgp_time_next_launch(void* start_event, void* stop_event) {
   return DGP_OK;
 }
 
-int dgp_launch_shape(const DgpHandle* h, int32_t batch, int32_t* lpt, int32_t* c) {
-  if (!h || batch <= 0) return fail(DGP_EINVAL, "null handle or non-positive batch");
-  const DgpShape sh = dgp_host::choose_shape(h, batch, h->base.qc_diag == 0 ? dgp_host::FAM_GENERAL : dgp_host::FAM_STATIC);      // (static covariances; per-call q_full tensors may pick another shape)
-  if (lpt) *lpt = sh.lpt;
-  if (c) *c = sh.c;
-  return DGP_OK;
-}
-
-int dgp_step_kernel_variant(const DgpHandle* h, int32_t batch) {
-  if (!h || batch <= 0) return fail(DGP_EINVAL, "null handle or non-positive batch");
-  return dgp_host::step_kernel_variant(h, batch);
-}
+int dgp_launch_shape(const DgpHandle* h, int32_t batch, int32_t* lpt, int32_t* c) { return dgp_host::launch_shape(h, batch, lpt, c); }
+int dgp_step_kernel_variant(const DgpHandle* h, int32_t batch) { return dgp_host::step_kernel_variant(h, batch); }
 
 int dgp_gn_step(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
                 const DgpCovs* covs, void* dtheta, void* err, void* err_ext, int32_t* info, void* stream) {
   dgp::GnParams p;
   int rc = dgp_host::fill_step(h, batch, th, start, goal, sdf, covs, dtheta, err, err_ext, info, p);
   if (rc != DGP_OK) return drop_events(rc);
-  hipError_t e = launch(h, dgp::MODE_STEP, p, nullptr, (hipStream_t)stream);
-  return hip_rc(e, "dgp_gn_step");
+  return launch(h, dgp_host::MODE_STEP, p, nullptr, (hipStream_t)stream, "dgp_gn_step");
 }
 
 int dgp_gn_solve(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf,
@@ -220,8 +203,7 @@ int dgp_gn_solve(const DgpHandle* h, int32_t batch, const void* th_init, const v
   int rc = dgp_host::fill_solve(h, batch, th_init, start, goal, sdf, covs, max_iters, tol_delta, th_out, iters, err_hist,
                                 errext_hist, err_final, info, p);
   if (rc != DGP_OK) return drop_events(rc);
-  hipError_t e = launch(h, dgp::MODE_SOLVE, p, nullptr, (hipStream_t)stream);
-  return hip_rc(e, "dgp_gn_solve");
+  return launch(h, dgp_host::MODE_SOLVE, p, nullptr, (hipStream_t)stream, "dgp_gn_solve");
 }
 
 int dgp_eval_errors(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
@@ -229,8 +211,7 @@ int dgp_eval_errors(const DgpHandle* h, int32_t batch, const void* th, const voi
   dgp::GnParams p;
   int rc = dgp_host::fill_eval(h, batch, th, start, goal, sdf, covs, err, err_ext, unw_sg, unw_gp, unw_obs, p);
   if (rc != DGP_OK) return drop_events(rc);
-  hipError_t e = launch(h, dgp::MODE_EVAL, p, nullptr, (hipStream_t)stream);
-  return hip_rc(e, "dgp_eval_errors");
+  return launch(h, dgp_host::MODE_EVAL, p, nullptr, (hipStream_t)stream, "dgp_eval_errors");
 }
 
 int dgp_gn_step_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
@@ -242,8 +223,7 @@ int dgp_gn_step_backward(const DgpHandle* h, int32_t batch, const void* th, cons
   int rc = dgp_host::fill_backward(h, batch, th, start, goal, sdf, covs, dtheta, g_dtheta, g_err_ext, g_th, g_start, g_goal, g_sdf,
                                    g_sdf_batch_stride, g_sdf_copies, g_qc_inv, g_obs_w, g_eps, p, g);
   if (rc != DGP_OK) return drop_events(rc);
-  hipError_t e = launch(h, dgp_dev::MODE_BACKWARD, p, &g, (hipStream_t)stream);
-  return hip_rc(e, "dgp_gn_step_backward");
+  return launch(h, dgp_host::MODE_BACKWARD, p, &g, (hipStream_t)stream, "dgp_gn_step_backward");
 }
 
 int dgp_eval_errors_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
@@ -255,17 +235,14 @@ int dgp_eval_errors_backward(const DgpHandle* h, int32_t batch, const void* th, 
   int rc = dgp_host::fill_eval_backward(h, batch, th, start, goal, sdf, covs, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start, g_goal,
                                         g_sdf, g_sdf_batch_stride, g_sdf_copies, g_eps, p, g);
   if (rc != DGP_OK) return drop_events(rc);
-  hipError_t e = launch(h, dgp_dev::MODE_BACKWARD, p, &g, (hipStream_t)stream);
-  return hip_rc(e, "dgp_eval_errors_backward");
+  return launch(h, dgp_host::MODE_BACKWARD, p, &g, (hipStream_t)stream, "dgp_eval_errors_backward");
 }
 
 // The round-4 entry points: their host logic (validation, the two launches behind one call) is shared with the test emulator, dgp_host.h
 namespace {
 struct HipLaunch {
   const DgpHandle* h; hipStream_t s; const char* what;
-  int operator()(int mode, const dgp::GnParams& p, const dgp::GnGradParams* g) const {
-    return hip_rc(launch(h, mode, p, g, s), what);
-  }
+  int operator()(int mode, const dgp::GnParams& p, const dgp::GnGradParams* g) const { return launch(h, mode, p, g, s, what); }
 };
 }  // namespace
 

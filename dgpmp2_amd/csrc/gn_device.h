@@ -223,148 +223,48 @@ __global__ void __launch_bounds__(64) gn_long_backward_kernel(const dgp::GnParam
   dgp::gn_long_backward_program<DOF, IO>(p, g, cx);
 }
 
-// every (LPT, C) of dgp_host::shape_supported; the tiled units (DGP_TL == 1) hold the two shapes dgp_host::choose_shape picks for tiled grids
-#if DGP_TL == 1 || DGP_STEP_ERRS == 1
-#define DGP_FOR_EACH_SHAPE(X) X(16, 4) X(32, 4)
-#else
-#define DGP_FOR_EACH_SHAPE(X) X(16, 1) X(32, 1) X(64, 1) X(16, 2) X(32, 2) X(64, 2) X(16, 4) X(32, 4) X(64, 4)
-#endif
-
-// mode: dgp::MODE_* or MODE_BACKWARD
-enum { MODE_BACKWARD = 3, MODE_CHAIN = 4 };      // MODE_CHAIN: dgp_gn_solve_backward (the chain kernels, static covariances)
-
-// The kernels are spread over translation units (gn_inst.hip, one per (dof, io dtype, group)) so that they build in
-// parallel.  Group of a launch: static-covariance STEP / SOLVE; the general-covariance STEP / SOLVE plus EVAL; the static and
-// general backward kernels; everything for per-state Q_c^-1 tensors (QK_KRON: STEP, SOLVE, backward).
-enum { GROUP_STATIC = 0, GROUP_GENERIC = 1, GROUP_BACKWARD = 2, GROUP_KRON = 3, GROUP_CHAIN = 4, NUM_GROUPS = 5 };
-inline int launch_group(int mode, const dgp::GnParams& p) {
-  if (mode == dgp::MODE_EVAL) return GROUP_GENERIC;
-  if (mode == MODE_CHAIN) return GROUP_CHAIN;
-  const int qk = dgp::kernel_variant(p);
-  if (qk == dgp::QK_SCALED) return mode == MODE_BACKWARD ? GROUP_BACKWARD : GROUP_STATIC;      // (STEP and the single-step backward, host-checked)
-  if (qk == dgp::QK_KRON) return GROUP_KRON;
-  if (mode == MODE_BACKWARD) return GROUP_BACKWARD;
-  return qk == dgp::QK_STATIC ? GROUP_STATIC : GROUP_GENERIC;
-}
-
-// (TL is part of the signature: the standard and the tiled unit of one (dof, io dtype, group) must not share ONE weak host instantiation of this template --
-//  the linker would keep either, and both launchers would then start the same kernels)
+// The launcher of one translation unit (gn_inst.hip: one per unit family, dof, io dtype and group): starts the kernel dgp_host::choose_kernel picked, which this
+// unit must hold.  The kernels a unit instantiates are those dgp_host::kernel_built names for it, through dgp_host::with_kernel_args.
+// (TL, the unit family, is part of the signature: the standard and the twin units of one (dof, io dtype, group) must not share ONE weak host instantiation of this
+//  template -- the linker would keep either, and both launchers would then start the same kernels)
 template <int DOF, typename IO, int GROUP, int TL = DGP_TL + 2 * DGP_STEP_ERRS>
-hipError_t launch_typed(DgpShape sh, int mode, const dgp::GnParams& p, const dgp::GnGradParams* g, hipStream_t s) {
-  const int tpw = 64 / sh.lpt;
+hipError_t launch_typed(const dgp_host::KernelChoice& kc, const dgp::GnParams& p, const dgp::GnGradParams* g, hipStream_t s) {
+  if (kc.unit != TL || kc.group != GROUP) return hipErrorInvalidValue;
+  const int tpw = 64 / kc.sh.lpt;
   const dim3 grid((unsigned)((p.B + tpw - 1) / tpw)), block(64);
-  const bool qstat = dgp::use_static_kernels(p);
-  if (launch_group(mode, p) != GROUP) return hipErrorInvalidValue;
   // dgp_time_next_launch(): this launch records its own begin / end on the caller's events (hipExtLaunchKernelGGL); one-shot
   dgp_host::LaunchEvents& le = dgp_host::launch_events();
   const hipEvent_t ev0 = (hipEvent_t)le.start, ev1 = (hipEvent_t)le.stop;
   const bool timed = ev0 && ev1;
   le.start = le.stop = nullptr;
-#define DGP_LAUNCH(K)                                                               \
-  do {                                                                              \
-    if (timed) hipExtLaunchKernelGGL(K, grid, block, 0, s, ev0, ev1, 0, p);         \
-    else hipLaunchKernelGGL(K, grid, block, 0, s, p);                               \
-  } while (0)
-#define DGP_LAUNCH_BWD(K)                                                           \
-  do {                                                                              \
-    if constexpr (DGP_STEP_ERRS == 0) {                                             \
-      if (timed) hipExtLaunchKernelGGL(K, grid, block, 0, s, ev0, ev1, 0, p, *g);   \
-      else hipLaunchKernelGGL(K, grid, block, 0, s, p, *g);                         \
-    } else return hipErrorInvalidValue;                                             \
-  } while (0)
-  /* the step-errors twins hold MODE_STEP kernels only: every other launch is a discarded statement there (no instantiation) */
-#define DGP_LAUNCH_NOSTEP(K)                                                        \
-  do {                                                                              \
-    if constexpr (DGP_STEP_ERRS == 0) DGP_LAUNCH(K); else return hipErrorInvalidValue; \
-  } while (0)
-#define DGP_CASE(L, CC)                                                                                                   \
-  if (sh.lpt == L && sh.c == CC) {                                                                                         \
-    if constexpr (GROUP == GROUP_STATIC) {                                                                                 \
-      if (dgp::kernel_variant(p) == dgp::QK_SCALED) {                                                                      \
-        if (mode != dgp::MODE_STEP) return hipErrorInvalidValue;                                                           \
-        DGP_LAUNCH((gn_kernel<DOF, L, CC, IO, dgp::MODE_STEP, dgp::QK_SCALED>));                                           \
-        return hipGetLastError();                                                                                          \
-      }                                                                                                                    \
-      if constexpr (CC == 4) {                                                                                             \
-        if (dgp::wb_applies(p, L, CC)) {                                                                                   \
-          if (p.n == L * CC) {                                                                                             \
-            if (mode == dgp::MODE_STEP) DGP_LAUNCH((gn_kernel<DOF, L, CC, IO, dgp::MODE_STEP, dgp::QK_WB>));               \
-            else DGP_LAUNCH_NOSTEP((gn_kernel<DOF, L, CC, IO, dgp::MODE_SOLVE, dgp::QK_WB>));                                     \
-          } else {                                                                                                         \
-            if (mode == dgp::MODE_STEP) DGP_LAUNCH((gn_kernel<DOF, L, CC, IO, dgp::MODE_STEP, dgp::QK_WBR>));              \
-            else DGP_LAUNCH_NOSTEP((gn_kernel<DOF, L, CC, IO, dgp::MODE_SOLVE, dgp::QK_WBR>));                                    \
-          }                                                                                                                \
-          return hipGetLastError();                                                                                        \
-        }                                                                                                                  \
-      }                                                                                                                    \
-      /* (round 6: the d = 6 block-elimination twin is back -- its wrong results were the exec-join miscompile the build now repairs, profiles/r06_compiler_fault.md; */ \
-      /*  -DDGP_EXCLUDE_REPAIRED_TWINS=1 restores the round-5 exclusions of the two twins for the reproducer builds) */ \
-      if constexpr (DGP_STEP_ERRS == 1 && DOF == 3 && DGP_EXCLUDE_REPAIRED_TWINS) return hipErrorInvalidValue; \
-      else if (mode == dgp::MODE_STEP) DGP_LAUNCH((gn_kernel<DOF, L, CC, IO, dgp::MODE_STEP, dgp::QK_STATIC>));            \
-      else DGP_LAUNCH_NOSTEP((gn_kernel<DOF, L, CC, IO, dgp::MODE_SOLVE, dgp::QK_STATIC>));                                       \
-    } else if constexpr (GROUP == GROUP_GENERIC) {                                                                         \
-      if constexpr (DGP_STEP_ERRS == 1 && L == 32 && sizeof(IO) == 4 && DGP_EXCLUDE_REPAIRED_TWINS) return hipErrorInvalidValue;      \
-      else if (mode == dgp::MODE_STEP) DGP_LAUNCH((gn_kernel<DOF, L, CC, IO, dgp::MODE_STEP, dgp::QK_GENERAL>));           \
-      else if (mode == dgp::MODE_SOLVE) DGP_LAUNCH_NOSTEP((gn_kernel<DOF, L, CC, IO, dgp::MODE_SOLVE, dgp::QK_GENERAL>));  \
-      else DGP_LAUNCH_NOSTEP((gn_kernel<DOF, L, CC, IO, dgp::MODE_EVAL, dgp::QK_GENERAL>));                                \
-    } else if constexpr (GROUP == GROUP_CHAIN) {                                                                           \
-      if (p.qc_mode != dgp::QC_STATIC) return hipErrorInvalidValue;                                                        \
-      if (!qstat) {      /* round 6: a NON-DIAGONAL static Q_c_inv -- the general-covariance chain kernels (no covariance gradient: static) */ \
-        DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_GENERAL, true>));                                       \
-        return hipGetLastError();                                                                                          \
-      }                                                                                                                    \
-      if constexpr (CC == 4) {                                                                                             \
-        if (dgp::wb_applies(p, L, CC)) {                                                                                   \
-          if (p.n == L * CC) DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_WB, true>));                       \
-          else DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_WBR, true>));                                    \
-          return hipGetLastError();                                                                                        \
-        }                                                                                                                  \
-      }                                                                                                                    \
-      DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_STATIC, true>));                                          \
-    } else if constexpr (GROUP == GROUP_KRON) {                                                                            \
-      if (mode == dgp::MODE_STEP) DGP_LAUNCH((gn_kernel<DOF, L, CC, IO, dgp::MODE_STEP, dgp::QK_KRON>));                   \
-      else if (mode == dgp::MODE_SOLVE) DGP_LAUNCH_NOSTEP((gn_kernel<DOF, L, CC, IO, dgp::MODE_SOLVE, dgp::QK_KRON>));     \
-      else DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_KRON>));                                             \
-    } else {                                                                                                               \
-      if (dgp::kernel_variant(p) == dgp::QK_SCALED) {                                                                      \
-        DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_SCALED>));                                              \
-        return hipGetLastError();                                                                                          \
-      }                                                                                                                    \
-      if constexpr (CC == 4) {                                                                                             \
-        if (qstat && dgp::wb_applies(p, L, CC)) {                                                                          \
-          if (p.n == L * CC) DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_WB>));                             \
-          else DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_WBR>));                                          \
-          return hipGetLastError();                                                                                        \
-        }                                                                                                                  \
-      }                                                                                                                    \
-      if (qstat) DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_STATIC>));                                     \
-      else DGP_LAUNCH_BWD((gn_backward_kernel<DOF, L, CC, IO, dgp::QK_GENERAL>));                                          \
-    }                                                                                                                      \
-    return hipGetLastError();                                                                                              \
-  }
-  DGP_FOR_EACH_SHAPE(DGP_CASE)
-#undef DGP_CASE
-#undef DGP_LAUNCH
-#undef DGP_LAUNCH_NOSTEP
-#undef DGP_LAUNCH_BWD
-  return hipErrorInvalidValue;
+  const bool held = dgp_host::with_kernel_args<TL, GROUP, DOF, IO>(kc, [&](auto k) {
+    typedef decltype(k) K;
+    if constexpr (K::MODE == dgp_host::MODE_BACKWARD) {
+      if (timed) hipExtLaunchKernelGGL((gn_backward_kernel<DOF, K::LPT, K::C, IO, K::QK, K::CHAIN>), grid, block, 0, s, ev0, ev1, 0, p, *g);
+      else hipLaunchKernelGGL((gn_backward_kernel<DOF, K::LPT, K::C, IO, K::QK, K::CHAIN>), grid, block, 0, s, p, *g);
+    } else {
+      if (timed) hipExtLaunchKernelGGL((gn_kernel<DOF, K::LPT, K::C, IO, K::MODE, K::QK>), grid, block, 0, s, ev0, ev1, 0, p);
+      else hipLaunchKernelGGL((gn_kernel<DOF, K::LPT, K::C, IO, K::MODE, K::QK>), grid, block, 0, s, p);
+    }
+  });
+  return held ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace dgp_dev
 
-// One translation unit per (dof, io dtype, group) -- see gn_inst.hip.
-typedef hipError_t (*DgpLaunchFn)(DgpShape, int, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t);
-#define DGP_DECL_INST(d, t) \
-  hipError_t dgp_launch_##d##_##t##_g0(DgpShape, int, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t); \
-  hipError_t dgp_launch_##d##_##t##_g1(DgpShape, int, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t); \
-  hipError_t dgp_launch_##d##_##t##_g2(DgpShape, int, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t); \
-  hipError_t dgp_launch_##d##_##t##_g3(DgpShape, int, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t); \
-  hipError_t dgp_launch_##d##_##t##_g4(DgpShape, int, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t);
-DGP_DECL_INST(2, f32) DGP_DECL_INST(2, f64) DGP_DECL_INST(3, f32) DGP_DECL_INST(3, f64)
-// ... and their tiled twins (gn_inst.hip with -DDGP_TL=1): dgp_launch_<dof>t_<io>_g<group>
-DGP_DECL_INST(2t, f32) DGP_DECL_INST(2t, f64) DGP_DECL_INST(3t, f32) DGP_DECL_INST(3t, f64)
-// ... and the step-errors twins (gn_inst.hip with -DDGP_STEP_ERRS=1; groups 0 and 3 are built): dgp_launch_<dof>e_<io>_g<group>
-DGP_DECL_INST(2e, f32) DGP_DECL_INST(2e, f64) DGP_DECL_INST(3e, f32) DGP_DECL_INST(3e, f64)
-#undef DGP_DECL_INST
-// gn_long_inst.hip: the long-trajectory kernels of every (dof, io dtype); mode: dgp::MODE_* or dgp_dev::MODE_BACKWARD
+// One translation unit per (unit family, dof, io dtype, group) -- see gn_inst.hip; exactly the launchers of dgpmp2_amd/_build/units.py (tests/test_capi_load.py).
+typedef hipError_t DgpLaunch(const dgp_host::KernelChoice&, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t);
+DgpLaunch dgp_launch_2_f32_g0, dgp_launch_2_f32_g1, dgp_launch_2_f32_g2, dgp_launch_2_f32_g3, dgp_launch_2_f32_g4;
+DgpLaunch dgp_launch_2_f64_g0, dgp_launch_2_f64_g1, dgp_launch_2_f64_g2, dgp_launch_2_f64_g3, dgp_launch_2_f64_g4;
+DgpLaunch dgp_launch_3_f32_g0, dgp_launch_3_f32_g1, dgp_launch_3_f32_g2, dgp_launch_3_f32_g3, dgp_launch_3_f32_g4;
+DgpLaunch dgp_launch_3_f64_g0, dgp_launch_3_f64_g1, dgp_launch_3_f64_g2, dgp_launch_3_f64_g3, dgp_launch_3_f64_g4;
+// ... their tiled twins (gn_inst.hip with -DDGP_TL=1): dgp_launch_<dof>t_<io>_g<group>
+DgpLaunch dgp_launch_2t_f32_g0, dgp_launch_2t_f32_g1, dgp_launch_2t_f32_g2, dgp_launch_2t_f32_g3, dgp_launch_2t_f32_g4;
+DgpLaunch dgp_launch_2t_f64_g0, dgp_launch_2t_f64_g1, dgp_launch_2t_f64_g2, dgp_launch_2t_f64_g3, dgp_launch_2t_f64_g4;
+DgpLaunch dgp_launch_3t_f32_g0, dgp_launch_3t_f32_g1, dgp_launch_3t_f32_g2, dgp_launch_3t_f32_g3, dgp_launch_3t_f32_g4;
+DgpLaunch dgp_launch_3t_f64_g0, dgp_launch_3t_f64_g1, dgp_launch_3t_f64_g2, dgp_launch_3t_f64_g3, dgp_launch_3t_f64_g4;
+// ... and the step-errors twins (gn_inst.hip with -DDGP_STEP_ERRS=1: the groups with a step kernel; d = 6 without the general one): dgp_launch_<dof>e_<io>_g<group>
+DgpLaunch dgp_launch_2e_f32_g0, dgp_launch_2e_f32_g1, dgp_launch_2e_f32_g3, dgp_launch_2e_f64_g0, dgp_launch_2e_f64_g1, dgp_launch_2e_f64_g3;
+DgpLaunch dgp_launch_3e_f32_g0, dgp_launch_3e_f32_g3, dgp_launch_3e_f64_g0, dgp_launch_3e_f64_g3;
+// gn_long_inst.hip: the long-trajectory kernels of every (dof, io dtype); mode: dgp_host::MODE_STEP ... MODE_BACKWARD
 hipError_t dgp_launch_long(int dof, bool f64, int mode, const dgp::GnParams& p, const dgp::GnGradParams* g, hipStream_t s);

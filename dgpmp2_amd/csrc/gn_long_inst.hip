@@ -40,7 +40,7 @@ hipError_t launch_long_typed(int mode, const dgp::GnParams& p, const dgp::GnGrad
   if (mode == dgp::MODE_STEP) return launch_dyn(dgp_dev::gn_long_kernel<DOF, IO, dgp::MODE_STEP>, lds, p.B, s, p);
   if (mode == dgp::MODE_SOLVE) return launch_dyn(dgp_dev::gn_long_kernel<DOF, IO, dgp::MODE_SOLVE>, lds, p.B, s, p);
   if (mode == dgp::MODE_EVAL) return launch_dyn(dgp_dev::gn_long_kernel<DOF, IO, dgp::MODE_EVAL>, lds, p.B, s, p);
-  if (mode == dgp_dev::MODE_BACKWARD && g) return launch_dyn(dgp_dev::gn_long_backward_kernel<DOF, IO>, lds, p.B, s, p, *g);
+  if (mode == dgp_host::MODE_BACKWARD && g) return launch_dyn(dgp_dev::gn_long_backward_kernel<DOF, IO>, lds, p.B, s, p, *g);
   return hipErrorInvalidValue;
 }
 

@@ -43,7 +43,7 @@ def main():
     f.write('#include "%s"\n' % os.path.join(pipeline.CSRC, 'gn_device.h'))
     for u in UNITS:
       if u.launcher and u not in built:
-        f.write('hipError_t %s(DgpShape, int, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t) { return hipErrorInvalidValue; }\n' % u.launcher)
+        f.write('hipError_t %s(const dgp_host::KernelChoice&, const dgp::GnParams&, const dgp::GnGradParams*, hipStream_t) { return hipErrorInvalidValue; }\n' % u.launcher)
   stubs = pipeline.Job('stubs', stub, (), os.path.join(work, 'stubs', 'stubs.o'))
   # every unit through the product's own compile pipeline (pipeline.compile_hip_unit: device assembly, the exec-join repair, assembler, bundler, host object);
   # --raw: plain hipcc -c -save-temps (the unrepaired compiler output, for the reproducer builds of profiles/r06_compiler_fault.md); the stubs have no device code to repair

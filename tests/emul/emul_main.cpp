@@ -105,71 +105,34 @@ struct HostCtx {
   }
 };
 
-template <int DOF, int LPT, int C, typename IO>
-void run_wave(const dgp::GnParams& p, const dgp::GnGradParams* g, int mode, int wave) {
+// one wavefront of the lane program dgp_host::choose_kernel picked (K: dgp_host::KernelArgs -- the template arguments the product's launcher gives its kernel)
+template <typename K>
+void run_wave(const dgp::GnParams& p, const dgp::GnGradParams* g, int wave) {
   WaveShared ws;
   pthread_barrier_init(&ws.bar, nullptr, 64);
   std::vector<std::thread> th;
   for (int l = 0; l < 64; ++l) {
     th.emplace_back([&, l]() {
       HostCtx cx{&ws, l, wave};
-      // same dispatch as dgp_dev::launch_typed: the kernel variant follows the covariance representation
-      const int qk = dgp::kernel_variant(p);
-      if constexpr (C == 4) {      // the Woodbury kernels, chosen exactly as dgp_dev::launch_typed does
-        if (mode != dgp::MODE_EVAL && qk == dgp::QK_STATIC && dgp::wb_applies(p, LPT, C)) {
-          if (p.n == LPT * C) {
-            if (mode == dgp::MODE_STEP) dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_STEP, dgp::QK_WB>(p, cx);
-            else if (mode == dgp::MODE_SOLVE) dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_SOLVE, dgp::QK_WB>(p, cx);
-            else dgp::gn_backward_lane_program<DOF, LPT, C, IO, dgp::QK_WB>(p, *g, cx);
-          } else {
-            if (mode == dgp::MODE_STEP) dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_STEP, dgp::QK_WBR>(p, cx);
-            else if (mode == dgp::MODE_SOLVE) dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_SOLVE, dgp::QK_WBR>(p, cx);
-            else if (mode == 4) dgp::gn_backward_lane_program<DOF, LPT, C, IO, dgp::QK_WBR, true>(p, *g, cx);
-            else dgp::gn_backward_lane_program<DOF, LPT, C, IO, dgp::QK_WBR>(p, *g, cx);
-          }
-          return;
-        }
-      }
-      if (mode == dgp::MODE_STEP) {
-        if (qk == dgp::QK_STATIC) dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_STEP, dgp::QK_STATIC>(p, cx);
-        else if (qk == dgp::QK_SCALED) dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_STEP, dgp::QK_SCALED>(p, cx);
-        else if (qk == dgp::QK_KRON) dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_STEP, dgp::QK_KRON>(p, cx);
-        else dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_STEP, dgp::QK_GENERAL>(p, cx);
-      } else if (mode == dgp::MODE_SOLVE) {
-        if (qk == dgp::QK_STATIC) dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_SOLVE, dgp::QK_STATIC>(p, cx);
-        else if (qk == dgp::QK_KRON) dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_SOLVE, dgp::QK_KRON>(p, cx);
-        else dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_SOLVE, dgp::QK_GENERAL>(p, cx);
-      } else if (mode == dgp::MODE_EVAL) {
-        dgp::gn_lane_program<DOF, LPT, C, IO, dgp::MODE_EVAL, dgp::QK_GENERAL>(p, cx);
-      } else if (mode == 4) {      // (dgp_gn_solve_backward: static covariances only, host-checked; a non-diagonal Q_c_inv runs the general-covariance chain kernel)
-        if (qk == dgp::QK_STATIC) dgp::gn_backward_lane_program<DOF, LPT, C, IO, dgp::QK_STATIC, true>(p, *g, cx);
-        else dgp::gn_backward_lane_program<DOF, LPT, C, IO, dgp::QK_GENERAL, true>(p, *g, cx);
-      } else {
-        if (qk == dgp::QK_STATIC) dgp::gn_backward_lane_program<DOF, LPT, C, IO, dgp::QK_STATIC>(p, *g, cx);
-        else if (qk == dgp::QK_SCALED) dgp::gn_backward_lane_program<DOF, LPT, C, IO, dgp::QK_SCALED>(p, *g, cx);
-        else if (qk == dgp::QK_KRON) dgp::gn_backward_lane_program<DOF, LPT, C, IO, dgp::QK_KRON>(p, *g, cx);
-        else dgp::gn_backward_lane_program<DOF, LPT, C, IO, dgp::QK_GENERAL>(p, *g, cx);
-      }
+      if constexpr (K::MODE == dgp_host::MODE_BACKWARD) dgp::gn_backward_lane_program<K::DOF, K::LPT, K::C, typename K::IO, K::QK, K::CHAIN>(p, *g, cx);
+      else dgp::gn_lane_program<K::DOF, K::LPT, K::C, typename K::IO, K::MODE, K::QK>(p, cx);
     });
   }
   for (auto& t : th) t.join();
   pthread_barrier_destroy(&ws.bar);
 }
 
-#define EMUL_FOR_EACH_SHAPE(X) X(16, 1) X(32, 1) X(64, 1) X(16, 2) X(32, 2) X(64, 2) X(16, 4) X(32, 4) X(64, 4)
-
 template <int DOF, typename IO>
-void run_all(const dgp::GnParams& p, const dgp::GnGradParams* g, int mode, DgpShape sh) {
-  const int tpw = 64 / sh.lpt;
+int run_all(const dgp_host::KernelChoice& kc, const dgp::GnParams& p, const dgp::GnGradParams* g) {
+  const int tpw = 64 / kc.sh.lpt;
   const int waves = (p.B + tpw - 1) / tpw;
-  for (int w = 0; w < waves; ++w) {
-#define EMUL_CASE(L, CC) if (sh.lpt == L && sh.c == CC) run_wave<DOF, L, CC, IO>(p, g, mode, w);
-    EMUL_FOR_EACH_SHAPE(EMUL_CASE)
-#undef EMUL_CASE
-  }
+  const bool held = dgp_host::with_kernel_args<dgp_host::UNIT_ANY, dgp_host::GROUP_ANY, DOF, IO>(kc, [&](auto k) {
+    for (int w = 0; w < waves; ++w) run_wave<decltype(k)>(p, g, w);
+  });
+  return held ? DGP_OK : dgp_host::fail(DGP_EUNSUPPORTED, "emul: no lane program for this launch");
 }
 
-// long trajectories (gn_long.h): one trajectory per wavefront, the same dispatch as gn_long_inst.hip
+// long trajectories (gn_long.h): one trajectory per wavefront, the modes as gn_long_inst.hip launches them
 template <int DOF, typename IO>
 void run_long(const dgp::GnParams& p, const dgp::GnGradParams* g, int mode) {
   if (dgp::long_lds_bytes<2 * DOF>(p.n) > (int)sizeof(WaveShared::longb)) abort();
@@ -192,23 +155,18 @@ void run_long(const dgp::GnParams& p, const dgp::GnGradParams* g, int mode) {
   }
 }
 
-void run(const DgpHandle* h, const dgp::GnParams& p, const dgp::GnGradParams* g, int mode) {
-  if (p.sdf_layout != 0 && p.sdf && p.n > dgp_host::kMaxStatesTiled) {
-    fprintf(stderr, "emul: tiled grids are implemented for num_states <= 128 (the product library returns DGP_EUNSUPPORTED here)\n");
-    abort();
-  }
-  if (dgp_host::is_long(p.n)) {
-    const bool f64l = h->cfg.io_dtype == DGP_F64;
-    if (h->cfg.dof == 2) { if (f64l) run_long<2, double>(p, g, mode); else run_long<2, float>(p, g, mode); }
-    else { if (f64l) run_long<3, double>(p, g, mode); else run_long<3, float>(p, g, mode); }
-    return;
-  }
-  const bool step_errs = mode == (int)dgp_host::kModeStepErrs;      // dgp_gn_step_errors in one launch: MODE_STEP with the errors epilogue, on the twin kernels' shapes
-  if (step_errs) mode = dgp::MODE_STEP;
-  const DgpShape sh = dgp_host::choose_shape(h, p.B, dgp_host::shape_family(mode, p), step_errs || (p.sdf_layout != 0 && p.sdf != nullptr));      // (the shape the product launches)
+int run(const DgpHandle* h, const dgp::GnParams& p, const dgp::GnGradParams* g, int mode) {
+  dgp_host::KernelChoice kc;      // (the kernel and the shape the product launches)
+  const int rc = dgp_host::choose_kernel(h, mode, p, "emul", kc);
+  if (rc != DGP_OK) return rc;
   const bool f64 = h->cfg.io_dtype == DGP_F64;
-  if (h->cfg.dof == 2) { if (f64) run_all<2, double>(p, g, mode, sh); else run_all<2, float>(p, g, mode, sh); }
-  else { if (f64) run_all<3, double>(p, g, mode, sh); else run_all<3, float>(p, g, mode, sh); }
+  if (kc.is_long) {
+    if (h->cfg.dof == 2) { if (f64) run_long<2, double>(p, g, kc.mode); else run_long<2, float>(p, g, kc.mode); }
+    else { if (f64) run_long<3, double>(p, g, kc.mode); else run_long<3, float>(p, g, kc.mode); }
+    return DGP_OK;
+  }
+  if (h->cfg.dof == 2) return f64 ? run_all<2, double>(kc, p, g) : run_all<2, float>(kc, p, g);
+  return f64 ? run_all<3, double>(kc, p, g) : run_all<3, float>(kc, p, g);
 }
 
 }  // namespace
@@ -254,26 +212,15 @@ int emul_sdf_2d(const void*, int32_t, int32_t, int32_t, int32_t, int32_t, double
 }
 int emul_time_next_launch(void*, void*) { return DGP_OK; }      // nothing to time: the emulator runs on the host
 
-int emul_launch_shape(const DgpHandle* h, int32_t batch, int32_t* lpt, int32_t* c) {
-  if (!h || batch <= 0) return DGP_EINVAL;
-  const DgpShape sh = dgp_host::choose_shape(h, batch, h->base.qc_diag == 0 ? dgp_host::FAM_GENERAL : dgp_host::FAM_STATIC);
-  if (lpt) *lpt = sh.lpt;
-  if (c) *c = sh.c;
-  return DGP_OK;
-}
-
-int emul_step_kernel_variant(const DgpHandle* h, int32_t batch) {
-  if (!h || batch <= 0) return DGP_EINVAL;
-  return dgp_host::step_kernel_variant(h, batch);
-}
+int emul_launch_shape(const DgpHandle* h, int32_t batch, int32_t* lpt, int32_t* c) { return dgp_host::launch_shape(h, batch, lpt, c); }
+int emul_step_kernel_variant(const DgpHandle* h, int32_t batch) { return dgp_host::step_kernel_variant(h, batch); }
 
 int emul_gn_step(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
                  const DgpCovs* covs, void* dtheta, void* err, void* err_ext, int32_t* info, void*) {
   dgp::GnParams p;
   int rc = dgp_host::fill_step(h, batch, th, start, goal, sdf, covs, dtheta, err, err_ext, info, p);
   if (rc != DGP_OK) return rc;
-  run(h, p, nullptr, dgp::MODE_STEP);
-  return DGP_OK;
+  return run(h, p, nullptr, dgp_host::MODE_STEP);
 }
 
 int emul_gn_solve(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf,
@@ -283,8 +230,7 @@ int emul_gn_solve(const DgpHandle* h, int32_t batch, const void* th_init, const 
   int rc = dgp_host::fill_solve(h, batch, th_init, start, goal, sdf, covs, max_iters, tol_delta, th_out, iters, err_hist,
                                 errext_hist, err_final, info, p);
   if (rc != DGP_OK) return rc;
-  run(h, p, nullptr, dgp::MODE_SOLVE);
-  return DGP_OK;
+  return run(h, p, nullptr, dgp_host::MODE_SOLVE);
 }
 
 int emul_eval_errors(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
@@ -292,8 +238,7 @@ int emul_eval_errors(const DgpHandle* h, int32_t batch, const void* th, const vo
   dgp::GnParams p;
   int rc = dgp_host::fill_eval(h, batch, th, start, goal, sdf, covs, err, err_ext, unw_sg, unw_gp, unw_obs, p);
   if (rc != DGP_OK) return rc;
-  run(h, p, nullptr, dgp::MODE_EVAL);
-  return DGP_OK;
+  return run(h, p, nullptr, dgp_host::MODE_EVAL);
 }
 
 int emul_gn_step_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
@@ -305,8 +250,7 @@ int emul_gn_step_backward(const DgpHandle* h, int32_t batch, const void* th, con
   int rc = dgp_host::fill_backward(h, batch, th, start, goal, sdf, covs, dtheta, g_dtheta, g_err_ext, g_th, g_start, g_goal, g_sdf,
                                    g_sdf_batch_stride, g_sdf_copies, g_qc_inv, g_obs_w, g_eps, p, g);
   if (rc != DGP_OK) return rc;
-  run(h, p, &g, 3);
-  return DGP_OK;
+  return run(h, p, &g, dgp_host::MODE_BACKWARD);
 }
 
 int emul_eval_errors_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
@@ -318,14 +262,13 @@ int emul_eval_errors_backward(const DgpHandle* h, int32_t batch, const void* th,
   int rc = dgp_host::fill_eval_backward(h, batch, th, start, goal, sdf, covs, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start, g_goal,
                                         g_sdf, g_sdf_batch_stride, g_sdf_copies, g_eps, p, g);
   if (rc != DGP_OK) return rc;
-  run(h, p, &g, 3);
-  return DGP_OK;
+  return run(h, p, &g, dgp_host::MODE_BACKWARD);
 }
 
 namespace {
 struct EmulLaunch {
   const DgpHandle* h;
-  int operator()(int mode, const dgp::GnParams& p, const dgp::GnGradParams* g) const { run(h, p, g, mode); return DGP_OK; }      // (kModeStepErrs: run() maps it to MODE_STEP on a four-states-per-lane shape)
+  int operator()(int mode, const dgp::GnParams& p, const dgp::GnGradParams* g) const { return run(h, p, g, mode); }
 };
 }  // namespace
 

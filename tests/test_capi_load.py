@@ -28,21 +28,16 @@ def test_exports_every_declared_symbol(api):
 
 
 def test_launch_tables_reference_exactly_the_launchers_of_the_unit_table():
-  """The launch tables of dgpmp2_hip.hip and the unit table of the build (dgpmp2_amd/_build/units.py) are kept by hand and must agree: a launcher the tables name but no
-  unit defines fails the link, one a unit defines but no table names is dead weight.  gn_device.h declares every launcher of the tables, plus -- by the regularity of
-  DGP_DECL_INST -- ten step-errors launchers that are neither built nor called: groups 2 and 4 (backward kernels: no step to add an errors epilogue to) and d = 6 group 1
-  (the general twins units.py leaves out, with the measurement)."""
+  """The launch table of dgpmp2_hip.hip, the launcher declarations of gn_device.h and the unit table of the build (dgpmp2_amd/_build/units.py) are kept by hand and must
+  agree: a launcher the table names but no unit defines fails the link, one a unit defines but the table does not name is dead weight, and nothing is declared
+  that is not built (the table holds a null where a unit family has no such group)."""
   from dgpmp2_amd._build.units import LAUNCHERS
   csrc = os.path.join(ROOT, 'dgpmp2_amd', 'csrc')
   strip = lambda text: re.sub(r'//[^\n]*|/\*.*?\*/', '', text, flags=re.S)
-  referenced = set(re.findall(r'\bdgp_launch_[23][te]?_f(?:32|64)_g\d\b', strip(open(os.path.join(csrc, 'dgpmp2_hip.hip')).read())))
-  hdr = strip(open(os.path.join(csrc, 'gn_device.h')).read())
-  per_group = re.findall(r'dgp_launch_##d##_##t##_(g\d)\(', hdr[hdr.index('#define DGP_DECL_INST(d, t)'):hdr.index('#undef DGP_DECL_INST')])
-  declared = set('dgp_launch_%s_%s_%s' % (d, t, g) for d, t in re.findall(r'\bDGP_DECL_INST\(([23][te]?), (f32|f64)\)', hdr) for g in per_group)
+  names = lambda f: set(re.findall(r'\bdgp_launch_[23][te]?_f(?:32|64)_g\d\b', strip(open(os.path.join(csrc, f)).read())))
+  referenced, declared = names('dgpmp2_hip.hip'), names('gn_device.h')
   assert len(LAUNCHERS) == len(set(LAUNCHERS)) == 50
-  assert referenced == set(LAUNCHERS)
-  declared_never_built = set('dgp_launch_%se_%s_g%d' % (d, t, g) for d, groups in ((2, (2, 4)), (3, (1, 2, 4))) for t in ('f32', 'f64') for g in groups)
-  assert declared - referenced == declared_never_built and referenced <= declared
+  assert declared == referenced == set(LAUNCHERS)
 
 
 def test_struct_layout_matches_header():

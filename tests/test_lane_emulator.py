@@ -121,6 +121,28 @@ def test_emul_backward_shapes(be, golden, force_shape, shape):
   PC.case_backward_golden(be, golden, 'f64')
 
 
+@pytest.mark.parametrize('n', [64, 63])
+def test_emul_chain_backward_woodbury_exact_and_ragged(be, force_shape, n):
+  """dgp_gn_solve_backward on the forced shape (16,4): n = 64 fills it (the QK_WB chain kernel), n = 63 does not (QK_WBR).  f64, B = 2, K = 2, against the
+  single-step backward launches chained by hand through the traced history (lane_mix.chain_walk), at lane_mix's bound for the static Woodbury chain.
+  The emulator must run the chain program the product launches here: before the kernel selection was shared, its own dispatch ran the single-step
+  backward program at n = 64, which reads the null dtheta of a chain call: the n = 64 case ended in a segmentation fault inside emul_gn_solve_backward."""
+  import lane_mix as LM
+  from dgpmp2_amd import _capi
+  force_shape('16,4')
+  bt = LM.make(2, 16, 4, n, 'static', waves=0, nan=False, io='f64', seed=n)
+  assert bt.B == 2
+  assert _capi.Solver(harness.config_from_oracle(bt.p, 'f64'), api=be.api).step_kernel_variant(bt.B) == LM.expected_variant(16, 4, n, 'static', False) == (3 if n == 64 else 4)
+  K = 2
+  tho, its, hist = be.solve_traced(bt.p, bt.th, bt.start, bt.goal, bt.sdf, K, 0.0, io='f64')[:3]
+  assert (its == K).all()
+  gbar = np.random.RandomState(7).randn(bt.B, n, 4)
+  got = be.solve_backward(bt.p, bt.start, bt.goal, bt.sdf, K, hist, tho, its, gbar, io='f64')
+  want = LM.chain_walk(be, bt, K, hist, tho, its, gbar, 'f64', 'dense')
+  bad = LM.check_grads(bt, 'chain backward vs chained steps', got, want, LM.CHAIN_TOL['static'], LM.ok_rows(bt), keys=('th', 'start', 'goal'))
+  assert not bad, '\n'.join(bad)
+
+
 def test_emul_woodbury_kernels(be, golden):
   """gn_woodbury.h on the emulator: the smallest shape in full, the two larger ones with one robot each (64 threads per wavefront)."""
   PC.case_woodbury_kernels(be, golden, 'f64', shapes=('16,4',), nb=2)
