@@ -23,7 +23,6 @@ Differences a caller can observe (all deliberate):
     in-place edit voids it); forward() / forward_with_errors() and their backward then launch the scaled-mask static kernels (DGP_QC_SCALAR) instead of the per-state
     ones.  Same values to rounding, the gradient returned for the tensor is that of its dof x dof blocks either way; a copy of the tensor (no tag) takes the per-state path.
 """
-import ctypes
 import weakref
 
 import torch
@@ -68,27 +67,9 @@ _cur_dev = getattr(torch._C, '_cuda_getDevice', None) or torch.cuda.current_devi
 _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None) or (lambda i: torch.cuda.current_stream(i).cuda_stream)
 
 
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _require_cuda(t, name):
   if not t.is_cuda:
     raise RuntimeError('dgpmp2_amd: `%s` must be a CUDA/ROCm tensor (got device %s); this build has no CPU path' % (name, t.device))
-
-
-class _NoGuard(object):
-  def __enter__(self): return self
-  def __exit__(self, *a): return False
-
-
-_NO_GUARD = _NoGuard()
-
-
-def _on_device(index):
-  """Context in which the CURRENT device is cuda:`index` (a launch goes to the current device's stream).  The usual case -- the tensors
-  already live on the current device -- costs one integer compare instead of torch.cuda.device()'s get / set / restore."""
-  return _NO_GUARD if index == _cur_dev() else torch.cuda.device(index)
 
 
 def _same_device(dev, **named):
@@ -111,102 +92,6 @@ def _launch(dev, fn, *args):
       rc = fn(*args)
   if rc:
     _capi.get_api().check(rc)
-
-
-class _GNStep(torch.autograd.Function):
-  """dtheta, err, err_ext = GN step; backward through dgp_gn_step_backward (adjoint block-tridiagonal solve)."""
-
-  @staticmethod
-  def launch(layer, static, th, start, goal, sdf, qc, ow, eps, own_info=False):
-    """The forward launch itself (no autograd bookkeeping): -> dth, err, eex, and what the backward needs (contiguous inputs,
-    the marshalled SDF / covariance arguments with the tensors they keep alive)."""
-    B = th.shape[0]
-    dtype = th.dtype
-    solver = layer._solvers.get(dtype) or layer._solver(dtype)
-    dev = th.get_device()
-    if start.get_device() != dev or goal.get_device() != dev:
-      _same_device(dev, startb=start, goalb=goal)
-    sd = layer._sdf_args(sdf, dtype, B, dev)
-    if static.__class__ is _RawCovs: cv = static.cov_args(B, dtype, dev)      # (qc is the learn module's raw output vector, squared inside the kernel)
-    else: cv = _NO_COVS_KEEP if static == _ALL_STATIC else layer._cov_args(qc, ow, eps, dtype, B, dev, static, True)
-    thc, stc, goc = th.contiguous(), start.contiguous(), goal.contiguous()
-    dth = torch.empty_like(thc)
-    proto = layer._err_protos.get((B, dtype, dev))
-    if proto is None: proto = layer._err_proto(B, dtype, dev, thc)
-    err = torch.empty_like(proto)           # (empty_like of a cached (B,1,1) tensor: 1.3 us; new_empty / torch.empty with a shape: 2.1 us)
-    eex = torch.empty_like(proto)
-    stream = _raw_stream(dev)
-    # SPD flags: a differentiable step (own_info) or a checking layer gets its own tensor -- `last_info` kept from iteration k stays that
-    # iteration's; the planning loop without an autograd graph reuses one buffer per (batch, device, stream), see _info_buffer
-    info = layer._info_buffer(B, dev, stream, thc)
-    if own_info or layer.check_spd: info = torch.empty_like(info)
-    _launch(dev, layer._pc.gn_step, solver.h, B, thc.data_ptr(), stc.data_ptr(), goc.data_ptr(), *sd[:7], *cv[:4], dth.data_ptr(), err.data_ptr(), eex.data_ptr(), info.data_ptr(), stream)
-    layer.__dict__['last_info'] = info      # (plain attribute: nn.Module.__setattr__ costs microseconds per call)
-    if layer.check_spd and bool(info.any()):
-      raise RuntimeError('dgpmp2_amd: A^T K A + delta I is not positive definite for %d of %d trajectories '
-                         '(the reference raises from torch.cholesky here)' % (int(info.sum()), B))
-    return dth, err, eex, (thc, stc, goc), (sd, cv)
-
-  @staticmethod
-  def forward(ctx, layer, static, slots, ts, box, *diff):
-    """ts = (th, start, goal, sdf, qc, ow, eps), every input; diff = those of them that require grad, ts[i] for i in slots.  Only `diff` are
-    tensor ARGUMENTS of the Function (the bookkeeping of Function.apply is paid per tensor argument: ~1 us each, and a TBPTT link
-    differentiates one of the seven); err -- never differentiable, plan_layer.py:275 -- leaves through `box` instead of as an output."""
-    th, start, goal, sdf, qc, ow, eps = ts
-    dth, err, eex, (thc, stc, goc), args = _GNStep.launch(layer, static, th, start, goal, sdf, qc, ow, eps, True)
-    box.append(err)
-    ctx.layer = layer
-    ctx.slots = slots
-    ctx.args = args                               # marshalled SDF / covariance arguments (and the converted copies they point into)
-    # Inputs: the backward needs their ADDRESSES (in ctx.args) and, for the gradient buffers, their shapes -- not SavedVariables, whose
-    # unpacking costs ~1.5 us per tensor.  What save_for_backward would add, the "modified by an inplace operation" check, is done
-    # by hand on the version counters.  (dth is an OUTPUT: it must go through save_for_backward, a plain reference would be a cycle.)
-    ctx.inputs = (thc, stc, goc, sdf, qc, ow, eps, start, goal)
-    ctx.versions = (thc._version, stc._version, goc._version, -1 if sdf is None else sdf._version, -1 if qc is None else qc._version,
-                    -1 if ow is None else ow._version, -1 if eps is None else eps._version)
-    ctx.save_for_backward(dth)
-    ctx.set_materialize_grads(False)              # an unused output arrives as None: no adjoint solve for an err_ext-only loss
-    return dth, eex
-
-  @staticmethod
-  def backward(ctx, g_dth, g_eex):
-    # The backward is a raw kernel: a double backward must raise instead of silently returning zeros.  torch's once_differentiable
-    # does that, at ~8 us of wrapper per call; grad mode is only enabled inside backward() under create_graph=True, so the wrapper
-    # is only paid there.
-    if torch.is_grad_enabled():
-      return _GNStep._backward_once(ctx, g_dth, g_eex)
-    return _GNStep._backward_impl(ctx, g_dth, g_eex)
-
-  @staticmethod
-  def _backward_impl(ctx, g_dth, g_eex):
-    layer = ctx.layer
-    dth, = ctx.saved_tensors
-    th, stc, goc, sdf, qc, ow, eps, start, goal = ctx.inputs
-    _check_versions(ctx.inputs, ctx.versions)
-    sd, cv = ctx.args
-    B, n, d = th.shape
-    dtype = th.dtype
-    solver = layer._solvers[dtype]
-    dev = th.get_device()
-    slots = ctx.slots
-    nig = ctx.needs_input_grad                    # (layer, static, slots, ts, box, *diff)
-    need = [False] * 9                            # indexed like the old fixed signature: [2 + i] <-> ts[i]
-    for q, i in enumerate(slots): need[2 + i] = nig[5 + q]
-    if g_dth is not None and (g_dth.dtype is not dtype or not g_dth.is_contiguous()): g_dth = g_dth.contiguous().to(dtype)
-    if g_eex is not None and (g_eex.dtype is not dtype or not g_eex.is_contiguous()): g_eex = g_eex.contiguous().to(dtype)
-    g_th = torch.empty_like(th) if need[2] else None
-    g_st = _grad_like(start, stc) if need[3] else None
-    g_go = _grad_like(goal, goc) if need[4] else None
-    gs = _SdfGrad(layer, th, sdf, sd) if need[5] else _NO_SDF_GRAD
-    g_qc = _grad_like(qc, th) if (need[6] and cv[1] is not None) else None
-    g_ow = _grad_like(ow, th) if (need[7] and cv[2] is not None) else None
-    g_eps = _grad_like(eps, th) if (need[8] and cv[3] is not None) else None
-    _launch(dev, layer._pc.gn_step_backward, solver.h, B, th.data_ptr(), stc.data_ptr(), goc.data_ptr(), *gs.sd(sd),
-            *cv[:4], dth.data_ptr(), _ptr(g_dth), _ptr(g_eex), _ptr(g_th), _ptr(g_st), _ptr(g_go), gs.ptr, gs.stride, gs.copies,
-            _ptr(g_qc), _ptr(g_ow), _ptr(g_eps), _raw_stream(dev))
-    g_sdf = gs.finish(sdf)
-    grads = (g_th, _grad_out(g_st, start), _grad_out(g_go, goal), g_sdf, _grad_out(g_qc, qc), _grad_out(g_ow, ow), _grad_out(g_eps, eps))
-    return (None, None, None, None, None) + tuple(grads[i] for i in slots)
 
 
 def _expand_base(t):
@@ -247,9 +132,6 @@ def _grad_out(g, ref):
   if g is None or g.shape == ref.shape: return g
   g = g.reshape(ref.shape)
   return g if g.dtype is ref.dtype else g.to(ref.dtype)
-
-
-_GNStep._backward_once = staticmethod(once_differentiable(_GNStep._backward_impl))
 
 
 class _SdfGrad(object):
@@ -350,14 +232,119 @@ _NO_SDF_GRAD = _NoSdfGrad()
 _SPARSE_MIN_DENSE_BYTES = 16 << 20      # 'auto': below this a zero-filled dense gradient costs a few microseconds and keeps the reference's layout
 
 
-class _GNStepErrors(torch.autograd.Function):
-  """One iteration of the reference's training loop as ONE autograd node (learning/train_planner.py:311-327): dtheta, err, err_ext of the
-  step AND the three unweighted errors at th + dtheta -- forward = dgp_gn_step_errors, backward = dgp_gn_step_errors_backward (one
-  launch each for the 2-D robot with a row-major grid and up to 128 / 256 states, two stream-ordered launches otherwise, behind one C-ABI call; no th + dtheta tensor,
-  no second Function.apply, no second trip through the autograd engine)."""
+def _diff_needs(ctx, slots, first, count):
+  """Which of a node's `count` inputs ts[i] need a gradient: only diff = [ts[i] for i in slots] are ARGUMENTS of the Function, from position `first` on."""
+  nig = ctx.needs_input_grad
+  need = [False] * count
+  for q, i in enumerate(slots): need[i] = nig[first + q]
+  return need
+
+
+def _cot(g, dtype):
+  """A cotangent as a launch reads it: of the launch dtype and contiguous (an unused output's stays None)."""
+  return g if (g is None or (g.dtype is dtype and g.is_contiguous())) else g.contiguous().to(dtype)
+
+
+def _versions(*ts):
+  return tuple([-1 if t is None else t._version for t in ts])
+
+
+def _backward_of(impl):
+  """The `backward` staticmethod of a node whose backward is a raw kernel: a double backward must raise instead of silently returning zeros.  torch's
+  once_differentiable does that, at ~8 us of wrapper per call; grad mode is only enabled inside backward() under create_graph=True, so the wrapper
+  is only paid there."""
+  once = once_differentiable(impl)
+
+  def backward(ctx, *cots):
+    if torch.is_grad_enabled():
+      return once(ctx, *cots)
+    return impl(ctx, *cots)
+  return staticmethod(backward)
+
+
+def _keep_step(ctx, layer, slots, r, sdf, covs, start, goal):
+  """What the backward of a step node needs of its forward launch `r` (_GNStep.launch's tuple); covs = the covariance inputs behind the grid in `ts`."""
+  thc, stc, goc = r[6]
+  ctx.layer, ctx.slots = layer, slots
+  ctx.args = r[7]                               # marshalled SDF / covariance arguments (and the converted copies they point into)
+  # Inputs: the backward needs their ADDRESSES (in ctx.args) and, for the gradient buffers, their shapes -- not SavedVariables, whose
+  # unpacking costs ~1.5 us per tensor.  What save_for_backward would add, the "modified by an inplace operation" check, is done
+  # by hand on the version counters.  (dth is an OUTPUT: it must go through save_for_backward, a plain reference would be a cycle.)
+  ctx.inputs = (thc, stc, goc, sdf) + covs + (start, goal)
+  ctx.versions = _versions(thc, stc, goc, sdf, *covs)
+  ctx.save_for_backward(r[0])
+  ctx.set_materialize_grads(False)              # an unused output arrives as None: no adjoint solve for an err_ext-only loss
+
+
+def _step_backward(ctx, need, g_dth, g_eex, g_err, g_covs):
+  """The backward launch of a step node: dgp_gn_step_backward, or -- g_err = the cotangents of the three unweighted errors, not None -- dgp_gn_step_errors_backward.
+  need[0:4]: which of th, start, goal, sdf get a gradient; g_covs: the three covariance-gradient buffers (or None), the caller's.  -> (g_th, g_start, g_goal, the _SdfGrad to finish() into g_sdf: the raw node's covariance launch goes first)"""
+  layer = ctx.layer
+  dth, = ctx.saved_tensors
+  _check_versions(ctx.inputs, ctx.versions)
+  th, stc, goc, sdf = ctx.inputs[:4]
+  start, goal = ctx.inputs[-2:]
+  sd, cv = ctx.args
+  B, n, d = th.shape
+  dtype = th.dtype
+  solver = layer._solvers[dtype]
+  dev = th.get_device()
+  g_dth, g_eex = _cot(g_dth, dtype), _cot(g_eex, dtype)
+  g_th = torch.empty_like(th) if need[0] else None
+  g_st = _grad_like(start, stc) if need[1] else None
+  g_go = _grad_like(goal, goc) if need[2] else None
+  g_qc, g_ow, g_eps = g_covs
+  if g_err is None:
+    gs = _SdfGrad(layer, th, sdf, sd) if need[3] else _NO_SDF_GRAD
+    _launch(dev, layer._pc.gn_step_backward, solver.h, B, th.data_ptr(), stc.data_ptr(), goc.data_ptr(), *gs.sd(sd),
+            *cv[:4], dth.data_ptr(), _ptr(g_dth), _ptr(g_eex), _ptr(g_th), _ptr(g_st), _ptr(g_go), gs.ptr, gs.stride, gs.copies,
+            _ptr(g_qc), _ptr(g_ow), _ptr(g_eps), _raw_stream(dev))
+  else:
+    g_usg, g_ugp, g_uobs = _cot(g_err[0], dtype), _cot(g_err[1], dtype), _cot(g_err[2], dtype)
+    errs = g_usg is not None or g_ugp is not None or g_uobs is not None
+    gs = _SdfGrad(layer, th, sdf, sd, passes=2 if errs else 1) if need[3] else _NO_SDF_GRAD      # (with error cotangents the grid is read at th + dtheta and at th)
+    # d = 4: the errors' backward runs as a prologue of the step's backward kernel (one launch, hand-over in LDS); the two-launch form of the (x, y, theta)
+    # robot and of long trajectories hands dL/d(th + dtheta) over in a workspace
+    ws = torch.empty_like(th) if (errs and (d != 4 or n > 256)) else None
+    _launch(dev, layer._pc.gn_step_errors_backward, solver.h, B, th.data_ptr(), stc.data_ptr(), goc.data_ptr(), *gs.sd(sd),
+            *cv[:4], dth.data_ptr(), _ptr(g_dth), _ptr(g_eex), _ptr(g_usg), _ptr(g_ugp), _ptr(g_uobs), _ptr(g_th), _ptr(g_st),
+            _ptr(g_go), gs.ptr, gs.stride, gs.copies, _ptr(g_qc), _ptr(g_ow), _ptr(g_eps), _ptr(ws), _raw_stream(dev))
+  return g_th, _grad_out(g_st, start), _grad_out(g_go, goal), gs
+
+
+def _covs_step_forward(ctx, with_errors, layer, static, slots, ts, box):
+  """forward of _GNStep / _GNStepErrors -> the launch's tuple.  ts = (th, start, goal, sdf, qc, ow, eps), every input; diff = those of them that require grad,
+  ts[i] for i in slots.  Only `diff` are tensor ARGUMENTS of the Function (the bookkeeping of Function.apply is paid per tensor argument: ~1 us each, and a TBPTT link
+  differentiates one of the seven); err -- never differentiable, plan_layer.py:275 -- leaves through `box` instead of as an output."""
+  th, start, goal, sdf, qc, ow, eps = ts
+  r = _GNStep.launch(layer, with_errors, static, th, start, goal, sdf, qc, ow, eps, True)
+  box.append(r[1])
+  _keep_step(ctx, layer, slots, r, sdf, (qc, ow, eps), start, goal)
+  return r
+
+
+def _covs_step_backward(ctx, g_dth, g_eex, g_err):
+  """backward of _GNStep / _GNStepErrors: the gradient buffers of the covariance tensors the launch streamed, the shared launch, the gradients of `diff`."""
+  slots = ctx.slots
+  need = _diff_needs(ctx, slots, 5, 7)            # (layer, static, slots, ts, box, *diff)
+  th, qc, ow, eps = ctx.inputs[0], ctx.inputs[4], ctx.inputs[5], ctx.inputs[6]
+  cv = ctx.args[1]
+  g_qc = _grad_like(qc, th) if (need[4] and cv[1] is not None) else None
+  g_ow = _grad_like(ow, th) if (need[5] and cv[2] is not None) else None
+  g_eps = _grad_like(eps, th) if (need[6] and cv[3] is not None) else None
+  g_th, g_st, g_go, gs = _step_backward(ctx, need, g_dth, g_eex, g_err, (g_qc, g_ow, g_eps))
+  grads = (g_th, g_st, g_go, gs.finish(ctx.inputs[3]), _grad_out(g_qc, qc), _grad_out(g_ow, ow), _grad_out(g_eps, eps))
+  return (None, None, None, None, None) + tuple(grads[i] for i in slots)
+
+
+class _GNStep(torch.autograd.Function):
+  """dtheta, err, err_ext = GN step; backward through dgp_gn_step_backward (adjoint block-tridiagonal solve)."""
 
   @staticmethod
-  def launch(layer, static, th, start, goal, sdf, qc, ow, eps, own_info=False):
+  def launch(layer, with_errors, static, th, start, goal, sdf, qc, ow, eps, own_info=False):
+    """The forward launch itself (no autograd bookkeeping): dgp_gn_step, or -- with_errors -- dgp_gn_step_errors, which also writes the three unweighted errors
+    at th + dtheta.  -> dth, err, eex, usg, ugp, uobs (the last three None without errors), and what the backward needs: the contiguous inputs, the marshalled
+    SDF / covariance arguments with the tensors they keep alive."""
     B = th.shape[0]
     dtype = th.dtype
     solver = layer._solvers.get(dtype) or layer._solver(dtype)
@@ -365,19 +352,27 @@ class _GNStepErrors(torch.autograd.Function):
     if start.get_device() != dev or goal.get_device() != dev:
       _same_device(dev, startb=start, goalb=goal)
     sd = layer._sdf_args(sdf, dtype, B, dev)
-    if static.__class__ is _RawCovs: cv = static.cov_args(B, dtype, dev)
+    if static.__class__ is _RawCovs: cv = static.cov_args(B, dtype, dev)      # (qc is the learn module's raw output vector, squared inside the kernel)
     else: cv = _NO_COVS_KEEP if static == _ALL_STATIC else layer._cov_args(qc, ow, eps, dtype, B, dev, static, True)
     thc, stc, goc = th.contiguous(), start.contiguous(), goal.contiguous()
     dth = torch.empty_like(thc)
     proto = layer._err_protos.get((B, dtype, dev))
     if proto is None: proto = layer._err_proto(B, dtype, dev, thc)
-    err, eex, usg, ugp, uobs = (torch.empty_like(proto) for _ in range(5))
+    err = torch.empty_like(proto)           # (empty_like of a cached (B,1,1) tensor: 1.3 us; new_empty / torch.empty with a shape: 2.1 us)
+    eex = torch.empty_like(proto)
     stream = _raw_stream(dev)
+    # SPD flags: a differentiable step (own_info) or a checking layer gets its own tensor -- `last_info` kept from iteration k stays that
+    # iteration's; the planning loop without an autograd graph reuses one buffer per (batch, device, stream), see _info_buffer
     info = layer._info_buffer(B, dev, stream, thc)
     if own_info or layer.check_spd: info = torch.empty_like(info)
-    _launch(dev, layer._pc.gn_step_errors, solver.h, B, thc.data_ptr(), stc.data_ptr(), goc.data_ptr(), *sd[:7], *cv[:4], dth.data_ptr(), err.data_ptr(), eex.data_ptr(), info.data_ptr(), usg.data_ptr(), ugp.data_ptr(),
-            uobs.data_ptr(), stream)
-    layer.__dict__['last_info'] = info
+    if with_errors:
+      usg, ugp, uobs = torch.empty_like(proto), torch.empty_like(proto), torch.empty_like(proto)
+      _launch(dev, layer._pc.gn_step_errors, solver.h, B, thc.data_ptr(), stc.data_ptr(), goc.data_ptr(), *sd[:7], *cv[:4], dth.data_ptr(), err.data_ptr(), eex.data_ptr(), info.data_ptr(),
+              usg.data_ptr(), ugp.data_ptr(), uobs.data_ptr(), stream)
+    else:
+      usg = ugp = uobs = None
+      _launch(dev, layer._pc.gn_step, solver.h, B, thc.data_ptr(), stc.data_ptr(), goc.data_ptr(), *sd[:7], *cv[:4], dth.data_ptr(), err.data_ptr(), eex.data_ptr(), info.data_ptr(), stream)
+    layer.__dict__['last_info'] = info      # (plain attribute: nn.Module.__setattr__ costs microseconds per call)
     if layer.check_spd and bool(info.any()):
       raise RuntimeError('dgpmp2_amd: A^T K A + delta I is not positive definite for %d of %d trajectories '
                          '(the reference raises from torch.cholesky here)' % (int(info.sum()), B))
@@ -385,60 +380,30 @@ class _GNStepErrors(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, layer, static, slots, ts, box, *diff):
-    th, start, goal, sdf, qc, ow, eps = ts
-    dth, err, eex, usg, ugp, uobs, (thc, stc, goc), args = _GNStepErrors.launch(layer, static, th, start, goal, sdf, qc, ow, eps, True)
-    box.append(err)
-    ctx.layer, ctx.slots, ctx.args = layer, slots, args
-    ctx.inputs = (thc, stc, goc, sdf, qc, ow, eps, start, goal)
-    ctx.versions = (thc._version, stc._version, goc._version, -1 if sdf is None else sdf._version, -1 if qc is None else qc._version,
-                    -1 if ow is None else ow._version, -1 if eps is None else eps._version)
-    ctx.save_for_backward(dth)
-    ctx.set_materialize_grads(False)
-    return dth, eex, usg, ugp, uobs
+    r = _covs_step_forward(ctx, False, layer, static, slots, ts, box)
+    return r[0], r[2]
+
+  def _impl(ctx, g_dth, g_eex):
+    return _covs_step_backward(ctx, g_dth, g_eex, None)
+
+  backward = _backward_of(_impl)
+
+
+class _GNStepErrors(torch.autograd.Function):
+  """One iteration of the reference's training loop as ONE autograd node (learning/train_planner.py:311-327): dtheta, err, err_ext of the
+  step AND the three unweighted errors at th + dtheta -- forward = dgp_gn_step_errors, backward = dgp_gn_step_errors_backward (one
+  launch each for the 2-D robot with a row-major grid and up to 128 / 256 states, two stream-ordered launches otherwise, behind one C-ABI call; no th + dtheta tensor,
+  no second Function.apply, no second trip through the autograd engine)."""
 
   @staticmethod
-  def backward(ctx, g_dth, g_eex, g_usg, g_ugp, g_uobs):
-    if torch.is_grad_enabled():
-      return _GNStepErrors._backward_once(ctx, g_dth, g_eex, g_usg, g_ugp, g_uobs)
-    return _GNStepErrors._backward_impl(ctx, g_dth, g_eex, g_usg, g_ugp, g_uobs)
+  def forward(ctx, layer, static, slots, ts, box, *diff):
+    r = _covs_step_forward(ctx, True, layer, static, slots, ts, box)
+    return r[0], r[2], r[3], r[4], r[5]
 
-  @staticmethod
-  def _backward_impl(ctx, g_dth, g_eex, g_usg, g_ugp, g_uobs):
-    layer = ctx.layer
-    dth, = ctx.saved_tensors
-    th, stc, goc, sdf, qc, ow, eps, start, goal = ctx.inputs
-    _check_versions(ctx.inputs, ctx.versions)
-    sd, cv = ctx.args
-    B, n, d = th.shape
-    dtype = th.dtype
-    solver = layer._solvers[dtype]
-    dev = th.get_device()
-    slots = ctx.slots
-    nig = ctx.needs_input_grad                    # (layer, static, slots, ts, box, *diff)
-    need = [False] * 9
-    for q, i in enumerate(slots): need[2 + i] = nig[5 + q]
-    fix = lambda g: g if (g is None or (g.dtype is dtype and g.is_contiguous())) else g.contiguous().to(dtype)
-    g_dth, g_eex, g_usg, g_ugp, g_uobs = fix(g_dth), fix(g_eex), fix(g_usg), fix(g_ugp), fix(g_uobs)
-    g_th = torch.empty_like(th) if need[2] else None
-    g_st = _grad_like(start, stc) if need[3] else None
-    g_go = _grad_like(goal, goc) if need[4] else None
-    errs = g_usg is not None or g_ugp is not None or g_uobs is not None
-    gs = _SdfGrad(layer, th, sdf, sd, passes=2 if errs else 1) if need[5] else _NO_SDF_GRAD      # (with error cotangents the grid is read at th + dtheta and at th)
-    g_qc = _grad_like(qc, th) if (need[6] and cv[1] is not None) else None
-    g_ow = _grad_like(ow, th) if (need[7] and cv[2] is not None) else None
-    g_eps = _grad_like(eps, th) if (need[8] and cv[3] is not None) else None
-    # d = 4: the errors' backward runs as a prologue of the step's backward kernel (one launch, hand-over in LDS); the two-launch form of the (x, y, theta)
-    # robot and of long trajectories hands dL/d(th + dtheta) over in a workspace
-    ws = torch.empty_like(th) if (errs and (d != 4 or n > 256)) else None
-    _launch(dev, layer._pc.gn_step_errors_backward, solver.h, B, th.data_ptr(), stc.data_ptr(), goc.data_ptr(), *gs.sd(sd),
-            *cv[:4], dth.data_ptr(), _ptr(g_dth), _ptr(g_eex), _ptr(g_usg), _ptr(g_ugp), _ptr(g_uobs), _ptr(g_th), _ptr(g_st),
-            _ptr(g_go), gs.ptr, gs.stride, gs.copies, _ptr(g_qc), _ptr(g_ow), _ptr(g_eps), _ptr(ws), _raw_stream(dev))
-    g_sdf = gs.finish(sdf)
-    grads = (g_th, _grad_out(g_st, start), _grad_out(g_go, goal), g_sdf, _grad_out(g_qc, qc), _grad_out(g_ow, ow), _grad_out(g_eps, eps))
-    return (None, None, None, None, None) + tuple(grads[i] for i in slots)
+  def _impl(ctx, g_dth, g_eex, g_usg, g_ugp, g_uobs):
+    return _covs_step_backward(ctx, g_dth, g_eex, (g_usg, g_ugp, g_uobs))
 
-
-_GNStepErrors._backward_once = staticmethod(once_differentiable(_GNStepErrors._backward_impl))
+  backward = _backward_of(_impl)
 
 
 class _RawCovs(object):
@@ -484,84 +449,43 @@ class _GNStepRaw(torch.autograd.Function):
   def forward(ctx, layer, raw, with_errors, slots, ts, box, *diff):
     th, start, goal, sdf, out = ts
     raw.square(layer._pc, th.get_device())
-    if with_errors:
-      dth, err, eex, usg, ugp, uobs, (thc, stc, goc), args = _GNStepErrors.launch(layer, raw, th, start, goal, sdf, out, None, None, True)
-    else:
-      dth, err, eex, (thc, stc, goc), args = _GNStep.launch(layer, raw, th, start, goal, sdf, out, None, None, True)
-      usg = ugp = uobs = None
+    r = _GNStep.launch(layer, with_errors, raw, th, start, goal, sdf, out, None, None, True)
     # (aliases as outputs: the node keeps raw.scal / ow / eps for its backward launch, and an OUTPUT held by its own node would be a reference cycle)
     qc, ow, eps = (None if t is None else t.view(t.shape) for t in (raw.qc, raw.ow, raw.eps))
-    box.append((err,))
-    ctx.layer, ctx.slots, ctx.args, ctx.raw, ctx.with_errors = layer, slots, args, raw, with_errors
-    ctx.inputs = (thc, stc, goc, sdf, out, start, goal)
-    ctx.versions = (thc._version, stc._version, goc._version, -1 if sdf is None else sdf._version, out._version)
-    ctx.save_for_backward(dth)
-    ctx.set_materialize_grads(False)
-    res = (dth, eex) + ((usg, ugp, uobs) if with_errors else ()) + tuple(t for t in (qc, ow, eps) if t is not None)
-    return res
+    box.append((r[1],))
+    _keep_step(ctx, layer, slots, r, sdf, (out,), start, goal)
+    ctx.raw, ctx.with_errors = raw, with_errors
+    return (r[0], r[2]) + (r[3:6] if with_errors else ()) + tuple(t for t in (qc, ow, eps) if t is not None)
 
-  @staticmethod
-  def backward(ctx, *cots):
-    if torch.is_grad_enabled():
-      return _GNStepRaw._backward_once(ctx, *cots)
-    return _GNStepRaw._backward_impl(ctx, *cots)
-
-  @staticmethod
-  def _backward_impl(ctx, *cots):
-    layer, raw = ctx.layer, ctx.raw
-    dth, = ctx.saved_tensors
-    th, stc, goc, sdf, out, start, goal = ctx.inputs
-    _check_versions(ctx.inputs[:5], ctx.versions)
-    sd, cv = ctx.args
-    B, n, d = th.shape
-    dtype = th.dtype
-    solver = layer._solvers[dtype]
-    dev = th.get_device()
-    slots = ctx.slots
-    nig = ctx.needs_input_grad                    # (layer, raw, with_errors, slots, ts, box, *diff)
-    need = [False] * 5
-    for q, i in enumerate(slots): need[i] = nig[6 + q]
-    fix = lambda g: g if (g is None or (g.dtype is dtype and g.is_contiguous())) else g.contiguous().to(dtype)
+  def _impl(ctx, *cots):
+    layer, raw, slots = ctx.layer, ctx.raw, ctx.slots
+    out = ctx.inputs[4]
+    need = _diff_needs(ctx, slots, 6, 5)          # (layer, raw, with_errors, slots, ts, box, *diff)
     k = 5 if ctx.with_errors else 2
-    g_dth, g_eex = fix(cots[0]), fix(cots[1])
-    g_usg, g_ugp, g_uobs = (fix(cots[2]), fix(cots[3]), fix(cots[4])) if ctx.with_errors else (None, None, None)
-    g_sq = list(cots[k:])                         # cotangents of the squared tensors (qc [if n_gp], ow, eps [if learn_eps]): normally all None
-    g_th = torch.empty_like(th) if need[0] else None
-    g_st = _grad_like(start, stc) if need[1] else None
-    g_go = _grad_like(goal, goc) if need[2] else None
-    errs = g_usg is not None or g_ugp is not None or g_uobs is not None
-    gs = _SdfGrad(layer, th, sdf, sd, passes=2 if errs else 1) if need[3] else _NO_SDF_GRAD
     g_out = gq = gw = ge = None
     if need[4]:
       # the backward kernel writes the gradients of the squared tensors (the blocks' gradient under DGP_QC_SCALAR); one more small launch turns them into d/d out
       if raw.n_gp: gq = torch.empty_like(raw.qc)
       gw = torch.empty_like(raw.ow)
       if raw.learn_eps: ge = torch.empty_like(raw.eps)
-    ws = torch.empty_like(th) if (errs and (d != 4 or n > 256)) else None
-    if ctx.with_errors:
-      _launch(dev, layer._pc.gn_step_errors_backward, solver.h, B, th.data_ptr(), stc.data_ptr(), goc.data_ptr(), *gs.sd(sd),
-              *cv[:4], dth.data_ptr(), _ptr(g_dth), _ptr(g_eex), _ptr(g_usg), _ptr(g_ugp), _ptr(g_uobs), _ptr(g_th), _ptr(g_st),
-              _ptr(g_go), gs.ptr, gs.stride, gs.copies, _ptr(gq), _ptr(gw), _ptr(ge), _ptr(ws), _raw_stream(dev))
-    else:
-      _launch(dev, layer._pc.gn_step_backward, solver.h, B, th.data_ptr(), stc.data_ptr(), goc.data_ptr(), *gs.sd(sd),
-              *cv[:4], dth.data_ptr(), _ptr(g_dth), _ptr(g_eex), _ptr(g_th), _ptr(g_st), _ptr(g_go), gs.ptr, gs.stride, gs.copies,
-              _ptr(gq), _ptr(gw), _ptr(ge), _raw_stream(dev))
+    g_th, g_st, g_go, gs = _step_backward(ctx, need, cots[0], cots[1], cots[2:5] if ctx.with_errors else None, (gq, gw, ge))
     if need[4]:
-      # someone differentiated the squared tensors themselves (the reference's loss does not): their cotangents join the kernel's gradients
+      # someone differentiated the squared tensors themselves (the reference's loss does not): their cotangents (qc [if n_gp], ow, eps [if learn_eps]: normally
+      # all None) join the kernel's gradients
+      dtype, dev = out.dtype, out.get_device()
       names = (['qc'] if raw.n_gp else []) + ['ow'] + (['eps'] if raw.learn_eps else [])
-      for name, g in zip(names, g_sq):
+      for name, g in zip(names, cots[k:]):
         if g is None: continue
         if name == 'qc': gq = gq + g.to(dtype)
         elif name == 'ow': gw = gw + g.reshape(gw.shape).to(dtype)
         else: ge = ge + g.reshape(ge.shape).to(dtype)
       g_out = torch.empty_like(out)
-      _launch(dev, layer._pc.square_covariances_backward, out.data_ptr(), _io_code(dtype), B, out.shape[2], raw.n_gp, raw.n, int(raw.learn_eps), raw.dof,
+      _launch(dev, layer._pc.square_covariances_backward, out.data_ptr(), _io_code(dtype), out.shape[0], out.shape[2], raw.n_gp, raw.n, int(raw.learn_eps), raw.dof,
               _ptr(gq), _ptr(gw), _ptr(ge), g_out.data_ptr(), _raw_stream(dev))
-    grads = (g_th, _grad_out(g_st, start), _grad_out(g_go, goal), gs.finish(sdf), g_out)
+    grads = (g_th, g_st, g_go, gs.finish(ctx.inputs[3]), g_out)
     return (None, None, None, None, None, None) + tuple(grads[i] for i in slots)
 
-
-_GNStepRaw._backward_once = staticmethod(once_differentiable(_GNStepRaw._backward_impl))
+  backward = _backward_of(_impl)
 
 
 class _GNSolve(torch.autograd.Function):
@@ -595,7 +519,7 @@ class _GNSolve(torch.autograd.Function):
     ctx.layer, ctx.slots, ctx.max_iters = layer, slots, max_iters
     ctx.args = sd
     ctx.inputs = (stc, goc, sdf, start, goal, thc)
-    ctx.versions = (stc._version, goc._version, -1 if sdf is None else sdf._version)
+    ctx.versions = _versions(stc, goc, sdf)
     ctx.hist, ctx.iters = hist, iters               # (work buffers of this node, never handed out: plain references)
     ctx.save_for_backward(th_out)
     return th_out
@@ -612,10 +536,8 @@ class _GNSolve(torch.autograd.Function):
     dtype = th_out.dtype
     solver = layer._solvers[dtype]
     dev = th_out.get_device()
-    nig = ctx.needs_input_grad                    # (layer, max_iters, tol_delta, slots, ts, box, *diff)
-    need = [False] * 4
-    for q, i in enumerate(ctx.slots): need[i] = nig[6 + q]
-    if g_out.dtype is not dtype or not g_out.is_contiguous(): g_out = g_out.contiguous().to(dtype)
+    need = _diff_needs(ctx, ctx.slots, 6, 4)      # (layer, max_iters, tol_delta, slots, ts, box, *diff)
+    g_out = _cot(g_out, dtype)
     g_th = torch.empty_like(th_out) if need[0] else None
     g_st = _grad_like(start, stc) if need[1] else None
     g_go = _grad_like(goal, goc) if need[2] else None
@@ -640,26 +562,19 @@ class _EvalErrors(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, layer, slots, ts, *diff):
-    """ts = (th, start, goal, sdf, eps); diff = ts[i] for i in slots, the inputs that require grad (see _GNStep.forward)."""
+    """ts = (th, start, goal, sdf, eps); diff = ts[i] for i in slots, the inputs that require grad (see _covs_step_forward)."""
     th, start, goal, sdf, eps = ts
     eps_arg = None if (eps is None or '_dgp_static' in eps.__dict__) else eps
     o, thc, stc, goc, sd, cv = layer._eval_launch(th, sdf, start, goal, None, None, eps_arg)
     ctx.layer = layer
     ctx.slots = slots
     ctx.args = (sd, cv)
-    ctx.inputs = (thc, stc, goc, sdf, eps_arg, start, goal)      # (addresses in ctx.args; version counters checked by hand, see _GNStep.forward)
-    ctx.versions = (thc._version, stc._version, goc._version, -1 if sdf is None else sdf._version, -1 if eps_arg is None else eps_arg._version)
+    ctx.inputs = (thc, stc, goc, sdf, eps_arg, start, goal)      # (addresses in ctx.args; version counters checked by hand, see _covs_step_forward)
+    ctx.versions = _versions(thc, stc, goc, sdf, eps_arg)
     ctx.set_materialize_grads(False)
     return o[1], o[2], o[3], o[4]            # (the three that read the grid are None without one)
 
-  @staticmethod
-  def backward(ctx, g_eex, g_usg, g_ugp, g_uobs):
-    if torch.is_grad_enabled():                       # create_graph=True: see _GNStep.backward
-      return _EvalErrors._backward_once(ctx, g_eex, g_usg, g_ugp, g_uobs)
-    return _EvalErrors._backward_impl(ctx, g_eex, g_usg, g_ugp, g_uobs)
-
-  @staticmethod
-  def _backward_impl(ctx, g_eex, g_usg, g_ugp, g_uobs):
+  def _impl(ctx, g_eex, g_usg, g_ugp, g_uobs):
     layer = ctx.layer
     th, stc, goc, sdf, eps, start, goal = ctx.inputs
     _check_versions(ctx.inputs, ctx.versions)
@@ -668,15 +583,13 @@ class _EvalErrors(torch.autograd.Function):
     dtype = th.dtype
     solver = layer._solvers[dtype]
     dev = th.get_device()
-    nig = ctx.needs_input_grad                        # (layer, slots, ts, *diff)
-    need = [False] * 6                                # indexed like the old fixed signature: [1 + i] <-> ts[i]
-    for q, i in enumerate(ctx.slots): need[1 + i] = nig[3 + q]
-    cot = [None if g is None else (g if (g.dtype is dtype and g.is_contiguous()) else g.contiguous().to(dtype)) for g in (g_eex, g_usg, g_ugp, g_uobs)]
-    g_th = torch.empty_like(th) if need[1] else None
-    g_st = _grad_like(start, stc) if need[2] else None
-    g_go = _grad_like(goal, goc) if need[3] else None
-    gs = _SdfGrad(layer, th, sdf, sd) if (sdf is not None and need[4]) else _NO_SDF_GRAD
-    g_eps = _grad_like(eps, th) if (need[5] and eps is not None) else None
+    need = _diff_needs(ctx, ctx.slots, 3, 5)          # (layer, slots, ts, *diff)
+    cot = [_cot(g, dtype) for g in (g_eex, g_usg, g_ugp, g_uobs)]
+    g_th = torch.empty_like(th) if need[0] else None
+    g_st = _grad_like(start, stc) if need[1] else None
+    g_go = _grad_like(goal, goc) if need[2] else None
+    gs = _SdfGrad(layer, th, sdf, sd) if (sdf is not None and need[3]) else _NO_SDF_GRAD
+    g_eps = _grad_like(eps, th) if (need[4] and eps is not None) else None
     _launch(dev, layer._pc.eval_errors_backward, solver.h, B, th.data_ptr(), stc.data_ptr(), goc.data_ptr(), *gs.sd(sd),
             *cv[:4], _ptr(cot[0]), _ptr(cot[1]), _ptr(cot[2]), _ptr(cot[3]), _ptr(g_th), _ptr(g_st), _ptr(g_go), gs.ptr,
             gs.stride, gs.copies, _ptr(g_eps), _raw_stream(dev))
@@ -684,8 +597,7 @@ class _EvalErrors(torch.autograd.Function):
     grads = (g_th, _grad_out(g_st, start), _grad_out(g_go, goal), g_sdf, _grad_out(g_eps, eps))
     return (None, None, None) + tuple(grads[i] for i in ctx.slots)
 
-
-_EvalErrors._backward_once = staticmethod(once_differentiable(_EvalErrors._backward_impl))
+  backward = _backward_of(_impl)
 
 
 class _AutoTile(torch.autograd.Function):
@@ -955,31 +867,39 @@ class PlanLayer(nn.Module):
     if startb.dtype is not dt or goalb.dtype is not dt:
       raise TypeError('thb, startb, goalb must share one dtype')
 
+  def _remember(self, startb, goalb, static, qc, ow, eps):
+    """Like the reference (plan_layer.py:88-94) remember means / covariances for the error_* helpers below.  start / goal / eps are kept WITH their graphs,
+    as set_mean / set_eps do: error_ext_batch and the unweighted errors are differentiable w.r.t. them; qc_inv / obscov_inv only feed error_batch, which runs
+    under no_grad, :275."""
+    if static == _ALL_STATIC:
+      self.__dict__['_last'] = (startb, goalb, None, None, None)
+    else:
+      self.__dict__['_last'] = (startb, goalb, None if (qc is None or static[0]) else qc.detach(), None if (ow is None or static[1]) else ow.detach(),
+                                None if (eps is None or static[2]) else eps)
+
+  @staticmethod
+  def _diff_slots(ts):
+    """ts = every input of a node, the grid at ts[3] -> (ts as the node should see them -- a grid that requires grad through _expand_base --, slots: the
+    indices of those that require grad; empty: no autograd node)."""
+    sdfb = ts[3]
+    if sdfb is not None and sdfb.requires_grad: ts = ts[:3] + (_expand_base(sdfb),) + ts[4:]
+    return ts, tuple([i for i, t in enumerate(ts) if t is not None and t.requires_grad])
+
   # -- the reference's public surface -----------------------------------------------------------------
   def forward(self, thb, startb, goalb, imb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb):
     """plan_layer.py:87-99.  -> (dthetab (B,n,d), err (B,1,1) [no grad], err_ext (B,1,1) [grad])."""
     self._check_inputs(thb, startb, goalb)
     if self.auto_tile: sdfb = self._auto_tiled(sdfb, thb.shape[0])
-    # like the reference (plan_layer.py:88-94) remember means / covariances for the error_* helpers below
     static = self.static_flags(qc_inv_trajb, obscov_inv_trajb, eps_trajb)
-    # (start / goal / eps are kept WITH their graphs, as set_mean / set_eps do: error_ext_batch and the unweighted errors are
-    #  differentiable w.r.t. them; qc_inv / obscov_inv only feed error_batch, which runs under no_grad, :275)
-    if static == _ALL_STATIC:
-      self.__dict__['_last'] = (startb, goalb, None, None, None)
-    else:
-      det = lambda t, st: None if (t is None or st) else t.detach()
-      self.__dict__['_last'] = (startb, goalb, det(qc_inv_trajb, static[0]), det(obscov_inv_trajb, static[1]),
-                                None if (eps_trajb is None or static[2]) else eps_trajb)
+    self._remember(startb, goalb, static, qc_inv_trajb, obscov_inv_trajb, eps_trajb)
     if torch.is_grad_enabled():
-      if sdfb is not None and sdfb.requires_grad: sdfb = _expand_base(sdfb)
-      ts = (thb, startb, goalb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb)
-      slots = tuple([i for i in range(7) if ts[i] is not None and ts[i].requires_grad])
+      ts, slots = self._diff_slots((thb, startb, goalb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb))
       if slots:
         box = []
         dth, eex = _GNStep.apply(self, static, slots, ts, box, *[ts[i] for i in slots])
         return dth, box[0], eex
     # planning / validation loops: no autograd node, one launch
-    return _GNStep.launch(self, static, thb, startb, goalb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb)[:3]
+    return _GNStep.launch(self, False, static, thb, startb, goalb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb)[:3]
 
   def forward_with_errors(self, thb, startb, goalb, imb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb):
     """forward() and, in the same call, what the reference's training loop evaluates right behind it (learning/train_planner.py:313,327):
@@ -994,21 +914,14 @@ class PlanLayer(nn.Module):
       sg, gp, ob = self.unweighted_errors(thb + dth, sdfb)
       return dth, err, eex, sg, gp, ob
     static = self.static_flags(qc_inv_trajb, obscov_inv_trajb, eps_trajb)
-    if static == _ALL_STATIC:
-      self.__dict__['_last'] = (startb, goalb, None, None, None)
-    else:
-      det = lambda t, st: None if (t is None or st) else t.detach()
-      self.__dict__['_last'] = (startb, goalb, det(qc_inv_trajb, static[0]), det(obscov_inv_trajb, static[1]),
-                                None if (eps_trajb is None or static[2]) else eps_trajb)
+    self._remember(startb, goalb, static, qc_inv_trajb, obscov_inv_trajb, eps_trajb)
     if torch.is_grad_enabled():
-      if sdfb is not None and sdfb.requires_grad: sdfb = _expand_base(sdfb)
-      ts = (thb, startb, goalb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb)
-      slots = tuple([i for i in range(7) if ts[i] is not None and ts[i].requires_grad])
+      ts, slots = self._diff_slots((thb, startb, goalb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb))
       if slots:
         box = []
         dth, eex, usg, ugp, uobs = _GNStepErrors.apply(self, static, slots, ts, box, *[ts[i] for i in slots])
         return dth, box[0], eex, usg.reshape(B, 1), ugp, uobs
-    dth, err, eex, usg, ugp, uobs = _GNStepErrors.launch(self, static, thb, startb, goalb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb)[:6]
+    dth, err, eex, usg, ugp, uobs = _GNStep.launch(self, True, static, thb, startb, goalb, sdfb, qc_inv_trajb, obscov_inv_trajb, eps_trajb)[:6]
     return dth, err, eex, usg.reshape(B, 1), ugp, uobs
 
   def raw_covs(self, out, mode, learn_eps):
@@ -1038,9 +951,7 @@ class PlanLayer(nn.Module):
       raise ValueError('the learn module output must share dtype, device and batch with thb')
     B = thb.shape[0]
     if torch.is_grad_enabled():
-      if sdfb is not None and sdfb.requires_grad: sdfb = _expand_base(sdfb)
-      ts = (thb, startb, goalb, sdfb, out)
-      slots = tuple([i for i in range(5) if ts[i] is not None and ts[i].requires_grad])
+      ts, slots = self._diff_slots((thb, startb, goalb, sdfb, out))
       if slots:
         box = []
         res = _GNStepRaw.apply(self, raw, with_errors, slots, ts, box, *[ts[i] for i in slots])
@@ -1056,10 +967,8 @@ class PlanLayer(nn.Module):
     raw.square(self._pc, thb.get_device())
     qc, ow, eps = raw.qc, raw.ow, raw.eps
     self.__dict__['_last'] = (startb, goalb, qc, ow, eps)
-    if with_errors:
-      dth, err, eex, usg, ugp, uobs = _GNStepErrors.launch(self, raw, thb, startb, goalb, sdfb, out, None, None)[:6]
-      return dth, err, eex, usg.reshape(B, 1), ugp, uobs, qc, ow, eps
-    dth, err, eex = _GNStep.launch(self, raw, thb, startb, goalb, sdfb, out, None, None)[:3]
+    dth, err, eex, usg, ugp, uobs = _GNStep.launch(self, with_errors, raw, thb, startb, goalb, sdfb, out, None, None)[:6]
+    if with_errors: return dth, err, eex, usg.reshape(B, 1), ugp, uobs, qc, ow, eps
     return dth, err, eex, qc, ow, eps
 
   def _eval_launch(self, thb, sdfb, startb, goalb, qc, ow, eps):
@@ -1110,9 +1019,7 @@ class PlanLayer(nn.Module):
     the autograd graph the reference's plain torch ops would carry: w.r.t. thb, sdfb, the start / goal means and the current eps."""
     if self.auto_tile: sdfb = self._auto_tiled(sdfb, thb.shape[0])
     if torch.is_grad_enabled():
-      if sdfb is not None and sdfb.requires_grad: sdfb = _expand_base(sdfb)
-      ts = (thb, st, go, sdfb, eps)
-      slots = tuple([i for i in range(5) if ts[i] is not None and ts[i].requires_grad])
+      ts, slots = self._diff_slots((thb, st, go, sdfb, eps))
       if slots:
         return _EvalErrors.apply(self, slots, ts, *[ts[i] for i in slots])
     o = self._eval(thb, sdfb, st, go, None, None, eps)
