@@ -47,6 +47,11 @@ class DgpCovs(C.Structure):
   _fields_ = [('qc_mode', C.c_int32), ('qc_inv', C.c_void_p), ('obs_w', C.c_void_p), ('eps', C.c_void_p)]
 
 
+class DgpSampleParams(C.Structure):
+  _fields_ = [('clearance', C.c_double), ('margin', C.c_double), ('min_dist_frac', C.c_double), ('near_tries', C.c_int32), ('max_draws', C.c_int32),
+              ('corner_inset', C.c_double)]
+
+
 class DgpError(RuntimeError):
   def __init__(self, code, msg):
     super(DgpError, self).__init__('dgpmp2_hip error %d: %s' % (code, msg))
@@ -58,7 +63,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -111,6 +116,11 @@ class CApi(object):
     if self.traj_metrics is not None:
       self.traj_metrics.restype = C.c_int
       self.traj_metrics.argtypes = [vp, i32, vp, C.POINTER(DgpSdf), dbl, vp, vp, vp, vp]
+    # dgp_sample_problems: like dgp_traj_metrics, no twin in the emulator
+    self.sample_problems = getattr(self.lib, prefix + 'sample_problems', None)
+    if self.sample_problems is not None:
+      self.sample_problems.restype = C.c_int
+      self.sample_problems.argtypes = [vp, i32, C.POINTER(DgpSdf), vp, C.POINTER(DgpSampleParams), C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     self.time_next_launch = f('time_next_launch'); self.time_next_launch.restype = C.c_int; self.time_next_launch.argtypes = [vp, vp]
     self.event_create = f('event_create'); self.event_create.restype = C.c_int; self.event_create.argtypes = [C.POINTER(vp)]
     self.event_destroy = f('event_destroy'); self.event_destroy.restype = None; self.event_destroy.argtypes = [vp]
@@ -355,6 +365,18 @@ class Solver(object):
     if self.api.traj_metrics is None:
       raise NotImplementedError('%s does not export %straj_metrics (the CPU emulator has no twin of the metrics kernel)' % (self.api.path, self.api.prefix))
     self.api.check(self.api.traj_metrics(self.handle, batch, th, C.byref(sdf), float(metric_eps), th_opt, metrics, obs_error, stream))
+
+  @staticmethod
+  def sample_params(clearance, margin=0.5, min_dist_frac=0.6, near_tries=15, max_draws=4096, corner_inset=0.2):
+    """DgpSampleParams with the constants of generate_optimal_paths_gpmp2.py:58-61, :77-80, :134-145; max_draws bounds the reference's endless loops."""
+    return DgpSampleParams(float(clearance), float(margin), float(min_dist_frac), int(near_tries), int(max_draws), float(corner_inset))
+
+  def sample_problems(self, batch, sdf, params, start, goal, th_init, seed=0, first_problem=0, env_index=None, diagonal=None, draws=None, info=None, stream=None):
+    """dgp_sample_problems: start / goal (B,1,4) and th_init (B,n,4) of the I/O type, draws (B,2) and info (B) int32, one launch."""
+    if self.api.sample_problems is None:
+      raise NotImplementedError('%s does not export %ssample_problems (the CPU emulator has no twin of the sampler kernel)' % (self.api.path, self.api.prefix))
+    self.api.check(self.api.sample_problems(self.handle, batch, C.byref(sdf) if sdf is not None else None, env_index, C.byref(params) if params is not None else None,
+                                            int(seed), int(first_problem), diagonal, start, goal, th_init, draws, info, stream))
 
   def eval_errors_backward(self, batch, th, start, goal, sdf, covs, g_err_ext=None, g_unw_sg=None, g_unw_gp=None, g_unw_obs=None,
                            g_th=None, g_start=None, g_goal=None, g_sdf=None, g_sdf_batch_stride=0, g_eps=None, stream=None, g_sdf_copies=1):

@@ -1,0 +1,118 @@
+"""Planning problems made on the device, and the reference's dataset-generation chain on top of them.
+
+Reference: datasets/generate_optimal_paths_gpmp2.py (get_random_2d_confs :54-81, generate_start_goal :120-162) and datasets/generate_2d_dataset.py (:205-265):
+images -> SDFs -> feasible start / goal pairs -> straight-line initial trajectories -> planner.forward() -> collision check -> files.  The reference finds the pairs in
+Python rejection loops, one Env2D.is_feasible call per candidate point; here every problem of a batch is sampled by ONE launch (dgp_sample_problems,
+csrc/problem_sampler.hip) with counter-based randomness: problem number p of a seed is the same problem whatever batch it is drawn in.  RRT* initialisation (OMPL),
+the obstacle-map generators and plotting are not part of this build: images are an input.
+"""
+import numpy as np
+import torch
+
+from .. import _capi
+from .planning_dataset import write_environment, write_problem, write_meta
+
+INFO_START_CAP, INFO_GOAL_CAP, INFO_NEAR_TRIES, INFO_DIAGONAL_REPLACED = 1, 2, 4, 8      # bits of `info` (include/dgpmp2_hip.h)
+
+
+class SampleInfo(object):
+  """What dgp_sample_problems reports per problem: `flags` (B,) int32 device tensor of INFO_* bits, `draws` (B,2) int32 device tensor (draw indices of the accepted
+  start and goal; -1 for a diagonal problem).  The properties are small torch ops on the device."""
+  __slots__ = ('flags', 'draws')
+
+  def __init__(self, flags, draws): self.flags, self.draws = flags, draws
+
+  @property
+  def capped(self): return (self.flags & (INFO_START_CAP | INFO_GOAL_CAP)) != 0
+
+  @property
+  def near_tries(self): return (self.flags & INFO_NEAR_TRIES) != 0
+
+  @property
+  def diagonal_replaced(self): return (self.flags & INFO_DIAGONAL_REPLACED) != 0
+
+
+def _layer(planner_or_layer):
+  return getattr(planner_or_layer, 'plan_layer', planner_or_layer)
+
+
+def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, clearance=None, seed=0, first_problem=0, diagonal=None, dtype=None, **params):
+  """Feasible start / goal pairs and straight-line initial trajectories for `num_problems` planning problems, one launch.
+  planner_or_layer: a DiffGPMP2Planner or its PlanLayer (dof 2).  sdfb: the signed distance fields as forward() takes them -- (E,1,H,W) (or (E,H,W), what sdf_2d_batch
+  returns), a utils.sdf_utils.TiledSdf, or a shared (1,1,H,W) / expand()ed grid; a host tensor raises, like sdf_2d_batch.  num_problems: default one per grid.
+  env_index (B,) integer device tensor: the grid each problem is sampled in (probs_per_env > 1 without copies of the grids); its entries are checked against the
+  number of grids (one small device -> host copy; not under HIP-graph capture, where the caller vouches for them).  clearance: a point is feasible where its signed
+  distance exceeds it; default sphere_radius + epsilon_dist + 0.1 (generate_optimal_paths_gpmp2.py:124).  (seed, first_problem + b) determine problem b.
+  diagonal (B,) integer device tensor: -1 random, 0..3 the corner-to-corner problem of :134-145.  dtype: of the outputs, default that of sdfb.
+  **params: margin (0.5), min_dist_frac (0.6), near_tries (15), max_draws (4096), corner_inset (0.2) -- _capi.DgpSampleParams.
+  -> (startb (B,1,4), goalb (B,1,4), th_initb (B,n,4), info: SampleInfo), device tensors."""
+  layer = _layer(planner_or_layer)
+  if not torch.is_tensor(sdfb) or not sdfb.is_cuda:
+    raise RuntimeError('dgpmp2_amd.sample_problems: `sdfb` must be a CUDA/ROCm tensor; this build has no CPU path')
+  if sdfb.dim() == 3: sdfb = sdfb.unsqueeze(1)
+  if dtype is None: dtype = sdfb.dtype
+  if clearance is None:
+    from ..gpmp2.plan_layer import _f
+    clearance = _f(layer.robot_model.get_sphere_radii()) + _f(layer.obs_params['epsilon_dist']) + 0.1
+  sp = _capi.Solver.sample_params(clearance, **params)
+  grids = int(sdfb.shape[0])
+  B = int(num_problems) if num_problems is not None else (int(env_index.shape[0]) if env_index is not None else grids)
+  if env_index is not None:
+    env_index = env_index.to(torch.int32)
+    shared = grids == 1 or sdfb.stride(0) == 0
+    if not shared and env_index.is_cuda and not torch.cuda.is_current_stream_capturing():
+      lo, hi = torch.aminmax(env_index)
+      if int(lo) < 0 or int(hi) >= grids: raise ValueError('env_index must lie in [0, %d), got values in [%d, %d]' % (grids, int(lo), int(hi)))
+  if diagonal is not None: diagonal = diagonal.to(torch.int32)
+  startb, goalb, th_initb, draws, info = layer.sample_problems(sdfb, B, sp, dtype, env_index, diagonal, seed, first_problem)
+  return startb, goalb, th_initb, SampleInfo(info, draws)
+
+
+def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, first_diagonal=True, require_collision_free=True, **params):
+  """The reference's generation chain for a batch of environments, on the device until the files are written:
+    1. sdf_2d_batch(images, padlen=0, res=cell_size)                              (generate_2d_dataset.py:211; cell_size = (x_max - x_min) / image width)
+    2. sample_problems: probs_per_env problems per environment; with first_diagonal the first problem of every environment is one of the four diagonals, drawn
+       from `seed`                                                                (generate_optimal_paths_gpmp2.py:126-148)
+    3. planner.forward on the straight-line initial trajectories                  (:181-184)
+    4. trajectory_metrics(eps=0): in_coll of every planned trajectory             (generate_2d_dataset.py:247-252)
+    5. write_environment / write_problem / write_meta
+  images: (E,H,W) or (E,1,H,W) device tensor, free space > 0.75.  An environment with a problem whose sampling hit max_draws is dropped; so is one with a planned
+  trajectory in collision when require_collision_free is set (the reference drops an environment by exception, :247-265).  Written environments are numbered densely.
+  **params go to sample_problems.  -> {'num_envs': written, 'kept': [input indices], 'dropped': {input index: reason}, 'start', 'goal', 'th_init', 'th_opt': device
+  tensors of ALL E * probs_per_env problems (problem e * probs_per_env + j), 'info': SampleInfo, 'in_coll': (E * probs_per_env,) bool}."""
+  from ..utils.sdf_utils import sdf_2d_batch
+  if not torch.is_tensor(images) or not images.is_cuda: raise RuntimeError('dgpmp2_amd.generate_dataset: `images` must be a CUDA/ROCm tensor; this build has no CPU path')
+  layer = planner.plan_layer
+  im = images[:, 0] if images.dim() == 4 else images
+  E, H, W = im.shape
+  P = int(probs_per_env)
+  x_lims, y_lims = [float(v) for v in planner.env_params['x_lims']], [float(v) for v in planner.env_params['y_lims']]
+  cell_size = (x_lims[1] - x_lims[0]) / W
+  sdf = sdf_2d_batch(im, padlen=0, res=cell_size).unsqueeze(1)      # (E,1,H,W) float64
+  B = E * P
+  env_index = torch.arange(E, device=im.device, dtype=torch.int32).repeat_interleave(P)
+  diagonal = torch.full((B,), -1, dtype=torch.int32, device=im.device)
+  if first_diagonal: diagonal[::P] = torch.from_numpy(np.random.RandomState(seed).randint(0, 4, E).astype(np.int32)).to(im.device)
+  startb, goalb, th_initb, info = sample_problems(layer, sdf, B, env_index=env_index, seed=seed, diagonal=diagonal, **params)
+  sdfb = sdf.index_select(0, env_index.long())      # one grid per problem, what forward() takes
+  imb = (im > 0.75).to(sdf.dtype).unsqueeze(1).index_select(0, env_index.long())
+  with torch.no_grad():
+    th_opt = planner.forward(th_initb, startb, goalb, imb, sdfb)[0]
+    in_coll = planner.trajectory_metrics(th_opt, sdfb, eps=0.0).in_collision
+  capped_h, coll_h = info.capped.view(E, P).any(1).cpu().numpy(), in_coll.view(E, P).any(1).cpu().numpy()
+  s_h, g_h, th_h = startb.cpu().numpy(), goalb.cpu().numpy(), th_opt.cpu().numpy()
+  im_h, sdf_h = (im > 0.75).to(torch.float64).cpu().numpy(), sdf[:, 0].cpu().numpy()
+  kept, dropped = [], {}
+  for e in range(E):
+    if capped_h[e]: dropped[e] = 'no feasible start / goal pair within max_draws candidates'
+    elif require_collision_free and coll_h[e]: dropped[e] = 'Trajectory is in collision'
+    else:
+      k = len(kept)
+      write_environment(root_dir, mode, k, im_h[e], sdf_h[e])
+      for j in range(P):
+        b = e * P + j
+        write_problem(root_dir, mode, k, j, s_h[b], g_h[b], th_h[b])
+      kept.append(e)
+  write_meta(root_dir, mode, len(kept), P, {'x_lims': x_lims, 'y_lims': y_lims}, W)
+  return {'num_envs': len(kept), 'kept': kept, 'dropped': dropped, 'start': startb, 'goal': goalb, 'th_init': th_initb, 'th_opt': th_opt, 'info': info,
+          'in_coll': in_coll}

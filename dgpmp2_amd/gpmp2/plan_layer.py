@@ -1078,6 +1078,44 @@ class PlanLayer(nn.Module):
     _launch(dev, self._pc.traj_metrics, solver.h, B, thc.data_ptr(), *sd[:7], float(eps), _ptr(opt), raw.data_ptr(), _ptr(oerr), _raw_stream(dev))
     return TrajectoryMetrics(raw, oerr)
 
+  def sample_problems(self, sdfb, num_problems, params, dtype=torch.float64, env_index=None, diagonal=None, seed=0, first_problem=0):
+    """Feasible start / goal pairs and their straight-line initial trajectories in ONE launch (dgp_sample_problems; datasets.problem_generation.sample_problems is the
+    documented front end and fills `params`, a _capi.DgpSampleParams).  sdfb as for forward() (row-major, TiledSdf, a shared grid); env_index (B) int32 device tensor:
+    the grid of sdfb each problem is sampled in (None: grid b / the shared grid), diagonal (B) int32 device tensor or None.
+    -> startb, goalb (B,1,4), th_initb (B,n,4) of `dtype`, draws (B,2) int32, info (B) int32, all on sdfb's device."""
+    if sdfb is None: raise ValueError('sample_problems needs the signed-distance grids (sdfb)')
+    _require_cuda(sdfb, 'sdfb')
+    B, dev = int(num_problems), sdfb.get_device()
+    solver = self._solvers.get(dtype) or self._solver(dtype)
+    grids = int(sdfb.shape[0])
+    shared = grids == 1 or sdfb.stride(0) == 0
+    if env_index is None and not shared and grids != B:
+      raise ValueError('sdfb has %d grids for %d problems: pass env_index (the grid of each problem)' % (grids, B))
+    sd = self._sdf_args(sdfb, dtype, B if (shared or env_index is None) else grids, dev)
+    keep = []
+
+    def index_arg(t, name):
+      if t is None: return None
+      _require_cuda(t, name)
+      if t.get_device() != dev: _same_device(dev, **{name: t})
+      if t.dtype is not torch.int32 or t.dim() != 1 or t.shape[0] != B: raise ValueError('%s must be an int32 tensor of shape (%d,), got %s %s' % (name, B, t.dtype, tuple(t.shape)))
+      t = t.contiguous()
+      keep.append(t)
+      return t.data_ptr()
+    ei, dg = index_arg(env_index, 'env_index'), index_arg(diagonal, 'diagonal')
+    device = sdfb.device
+    startb = torch.empty((B, 1, 4), dtype=dtype, device=device)
+    goalb = torch.empty((B, 1, 4), dtype=dtype, device=device)
+    th_initb = torch.empty((B, self.num_traj_states, 4), dtype=dtype, device=device)
+    draws = torch.empty((B, 2), dtype=torch.int32, device=device)
+    info = torch.empty((B,), dtype=torch.int32, device=device)
+    import ctypes
+    api = _capi.get_api()
+    arg = _capi.DgpSdf(*sd[:7])
+    _launch(dev, api.sample_problems, solver.h, B, ctypes.byref(arg), ei, ctypes.byref(params), int(seed), int(first_problem), dg, startb.data_ptr(), goalb.data_ptr(),
+            th_initb.data_ptr(), draws.data_ptr(), info.data_ptr(), _raw_stream(dev))
+    return startb, goalb, th_initb, draws, info
+
 
 class TrajectoryMetrics(object):
   """Result of PlanLayer.trajectory_metrics: `raw` is the (B, DGP_METRIC_COUNT) float64 device tensor dgp_traj_metrics wrote (columns _capi.METRIC_NAMES),

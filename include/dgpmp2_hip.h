@@ -348,6 +348,45 @@ int dgp_sdf_2d(const void* image, int32_t image_dtype, int32_t batch, int32_t ro
 int dgp_traj_metrics(const DgpHandle* h, int32_t batch, const void* th, const DgpSdf* sdf, double metric_eps, const void* th_opt,
                      double* metrics, void* obs_error, void* stream);
 
+/* Planning problems sampled on the device, ONE launch: for every problem of the batch a feasible start / goal pair and the straight-line initial trajectory between
+ * them -- what the reference's dataset generation does one point at a time in Python rejection loops:
+ *   get_random_2d_confs / generate_start_goal (datasets/generate_optimal_paths_gpmp2.py:54-81, :120-162) over Env2D.is_feasible (env/env_2d.py:86-90), i.e.
+ *   get_signed_obstacle_distance (:119-175) > eps, and straight_line_trajb (utils/planner_utils.py:47-56).
+ * dof == 2 handles only (the reference samples for ndims == 2 only): DGP_EINVAL otherwise, as for a NULL params / sdf, max_draws < 1 or a margin that leaves no box.
+ * sdf as for dgp_traj_metrics (row-major or DGP_SDF_TILED4, shared or one grid per sample).  env_index (B) int32 device array or NULL: the grid problem b is sampled
+ * in (several problems per environment without copies of the grids; every entry must name an existing grid); NULL: grid b (per-sample grids) / the shared grid.
+ * diagonal (B) int32 device array or NULL: 0..3 = the corner-to-corner problem of :134-145 (0: (x_min + inset, y_min + inset) -> (x_max - inset, y_max - inset), 1: the
+ * reverse, 2: (x_max - inset, y_min + inset) -> (x_min + inset, y_max - inset), 3: its reverse), replaced by a random problem when either corner is infeasible
+ * (:147-148; info bit 3); any other value (-1): a random problem.
+ * Feasibility of a point: dist(x, y) > clearance, dist = Env2D.get_signed_obstacle_distance in fp64 in the reference's operation order -- pixel coordinates
+ * orig + x / res, floor, the four indices clamped to the grid, the bilinear weights formed from the clamped indices as the reference forms them (on the last row /
+ * column both taps coincide and the weights cancel), MAX_D = x_max - x_min for a point outside the (closed) limits: the lookup of the step and metrics kernels.
+ * Randomness is counter-based -- Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (problem lo, problem hi, k, stream), problem = first_problem + b,
+ * stream 0 for start and 1 for goal candidates, k the draw index; the four output words give candidate k:
+ *   u0 = ((w0 * 2^32 | w1) >> 11) * 2^-53, u1 = ((w2 * 2^32 | w3) >> 11) * 2^-53, x = lbx + u0 (ubx - lbx), y = lby + u1 (uby - lby),
+ *   (lbx, lby) = (x_min + margin, y_min + margin), (ubx, uby) = (x_max - margin, y_max - margin)                                                 (:58-61)
+ * so a problem is a pure function of (seed, first_problem + b) and its grid: independent of batch size, position in the batch, launch shape and grid layout.
+ * The accepted start is the lowest k whose candidate is feasible (:63-67); the accepted goal is the lowest k whose candidate is feasible and either at distance
+ * sqrt(dx^2 + dy^2) >= min_dist_frac * ||(ubx, uby) - (lbx, lby)|| from the start or preceded by MORE than near_tries feasible-but-near goal candidates (:69-80: with
+ * near_tries = 15 the 17th such candidate is accepted).  Both loops stop after max_draws candidates (the reference loops for ever): the outputs then hold the last
+ * candidate drawn (k = max_draws - 1), the goal loop still runs after a capped start loop, and every output is written.
+ * Outputs, io_dtype, computed in fp64 and rounded once on store: start, goal (B,1,4) = [x, y, 0, 0]; th_init (B,n,4), rows i = 0 .. N = n - 1:
+ *   positions s*(N-i)*1.0/N*1.0 + g*i*1.0/N*1.0, velocities (g - s)/total_time_sec*1.0 (planner_utils.py:49-55, in that operation order).
+ * draws (B,2) int32 or NULL: the draw indices of the accepted start and goal (-1, -1 for a diagonal problem).  info (B) int32 or NULL: bit 0 the start loop hit
+ * max_draws, bit 1 the goal loop did, bit 2 the goal was accepted by the near-tries rule, bit 3 the diagonal was replaced by a random problem.
+ * One launch, no atomics, nothing allocated or synchronised: capturable in a HIP graph. */
+typedef struct DgpSampleParams {
+  double   clearance;      /* a point is feasible where dist(x, y) > clearance; the reference passes sphere_radius + epsilon_dist + 0.1 (generate_optimal_paths_gpmp2.py:124) */
+  double   margin;         /* sampling box = the handle's limits shrunk by margin on every side (0.5, :58-61) */
+  double   min_dist_frac;  /* goal wanted at least this fraction of the box diagonal away (0.6, :77) */
+  int32_t  near_tries;     /* a feasible but too-near goal is accepted once more than this many have been seen (15, :77-80) */
+  int32_t  max_draws;      /* bound on the draws of the start loop and of the goal loop; the reference loops for ever */
+  double   corner_inset;   /* 0.2, :134-145 */
+} DgpSampleParams;
+int dgp_sample_problems(const DgpHandle* h, int32_t batch, const DgpSdf* sdf, const int32_t* env_index,
+                        const DgpSampleParams* p, uint64_t seed, uint64_t first_problem, const int32_t* diagonal,
+                        void* start, void* goal, void* th_init, int32_t* draws, int32_t* info, void* stream);
+
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
  * hipExtLaunchKernelGGL does -- hipEventElapsedTime(start, stop) is then that kernel's execution time, the quantity
