@@ -996,64 +996,344 @@ def case_long_trajectories(be, golden, io, configs=None):
         A = rs.randn(B, n - 1, d, d) * 0.2; qc = (np.eye(d) + A @ np.swapaxes(A, -1, -2)) * 1.5; q_full = True
     r = lambda a: None if a is None else rnd(a, io)
     th, start, goal, sdf, qc, ow, eps = r(th), r(start), r(goal), r(sdf), r(qc), r(ow), r(eps)
-    kwc = dict(qc=qc, ow=ow, eps=eps, q_full=q_full)
-    tag = 'long: dof %d n %d %s %s' % (dof, n, cov, io)
-    tol = TOL[io] * (10 if n > 512 else 1)               # cond(Lambda) grows with n (dt^-3 in Q^-1): the fp64 oracles themselves differ by that much
-    # ---- one step, every trajectory against the block-tridiagonal C oracle
-    dth, err, eex, info = be.step(p, th, start, goal, sdf, io=io, **kwc)
-    c_dth, c_err, c_eex, c_info = BT.gn_step(p, th, start, goal, sdf, **kwc)
-    assert not info.any() and not c_info.any() and np.all(np.isfinite(dth)), tag
-    assert rel_err_per_traj(dth, c_dth) < tol, (tag, 'step', rel_err_per_traj(dth, c_dth))
-    assert rel_err(err, c_err) < TOL_ERR[io] and rel_err(eex, c_eex) < TOL_ERR[io], (tag, 'errors of the step')
-    # ---- the error evaluation against the step's own errors and the oracle's unweighted errors
-    e = be.eval_errors(p, th, start, goal, sdf, io=io, **kwc)
-    assert rel_err(e[0], c_err) < TOL_ERR[io] and rel_err(e[1], c_eex) < TOL_ERR[io], (tag, 'eval_errors')
-    sdfB = np.broadcast_to(sdf, (B,) + sdf.shape[1:])
-    import torch
-    usg, ugp, uob = AT.unweighted_errors(*[torch.from_numpy(np.array(a, dtype=np.float64)) for a in
-                                           (th, start, goal, sdfB, (p.static_covs(B)[2] if eps is None else eps.reshape(B, n, 1, 1)))], p)
-    for got, want, name in ((e[2], usg, 'sg'), (e[3], ugp, 'gp'), (e[4], uob, 'obs')):
-      assert rel_err(got, want.numpy().reshape(-1)) < TOL_ERR[io] * 10, (tag, 'unweighted ' + name, rel_err(got, want.numpy().reshape(-1)))
-    # ---- the fused loop equals chained steps (3 iterations; fp64 I/O: chained fp32 steps would round the state in between)
-    if io == 'f64' and n <= 512:
-      tho, its, eh, eeh, ef, sinfo = be.solve(p, th, start, goal, sdf, 3, 0.0, io=io, **kwc)
-      cur = th.copy()
-      for k in range(3):
-        d_k, e_k, x_k, i_k = be.step(p, cur, start, goal, sdf, io=io, **kwc)
-        assert rel_err(eh[:, k], e_k) < 1e-10 and rel_err(eeh[:, k], x_k) < 1e-10, (tag, 'history', k)
-        cur = cur + d_k
-      assert np.all(its == 3) and not sinfo.any() and rel_err(tho, cur) < 1e-9, (tag, 'fused loop', rel_err(tho, cur))
-      assert rel_err(ef, be.eval_errors(p, cur, start, goal, sdf, io=io, **kwc)[0]) < 1e-9, (tag, 'err_final')
-    # ---- backward of the step against torch autograd over the dense restatement (N = n d up to 1 920 here)
-    if n <= 320:
-      gbar = r(rs.randn(B, n, d)); gext = r(rs.randn(B))
-      shared = sdf.shape[0] == 1
-      g_h = be.backward(p, th, start, goal, sdf, rnd(dth, io), gbar, gext, io=io, sdf_copies=(16 if shared else 1), **kwc)
-      g_o = AT.step_gradients(p, th, start, goal, sdf, gbar, gext, **kwc)
-      for key in ('th', 'start', 'goal', 'sdf', 'qc', 'ow', 'eps'):
-        if g_h[key] is None or (key == 'sdf' and io == 'f32'): continue
-        a_ = g_h[key]
-        if key == 'sdf' and shared: a_ = a_.sum(0, keepdims=True)
-        b_ = g_o[key].reshape(a_.shape)
-        eb = np.abs(a_ - b_).max() / max(np.abs(b_).max(), np.abs(g_o['th']).max() if key == 'sdf' else 0.0, 1e-300)
-        assert eb < (1e-6 if io == 'f64' else 2e-3), (tag, 'backward', key, eb)
-      # ... and of the error evaluation (unweighted errors + err_ext), against autograd over the same restatement
-      cot = [r(rs.randn(B)) for _ in range(4)]
-      g_e = be.eval_backward(p, th, start, goal, sdf, g_err_ext=cot[0], g_unw_sg=cot[1], g_unw_gp=cot[2], g_unw_obs=cot[3], eps=eps, io=io,
-                             sdf_copies=(16 if shared else 1))
-      T = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
-      L = dict(th=T(th), start=T(start), goal=T(goal), sdf=T(sdf), eps=T(p.static_covs(B)[2] if eps is None else eps.reshape(B, n, 1, 1)))
-      for v in L.values(): v.requires_grad_(True)
-      sB = L['sdf'].expand(B, *L['sdf'].shape[1:]) if shared else L['sdf']
-      sq, so, se = p.static_covs(B)
-      _, _, eext = AT.plan_layer_forward(L['th'], L['start'], L['goal'], sB, T(sq), T(so), L['eps'], p)
-      usg, ugp, uob = AT.unweighted_errors(L['th'], L['start'], L['goal'], sB, L['eps'], p)
-      loss = (T(cot[0]) * eext.reshape(B)).sum() + (T(cot[1]) * usg.reshape(B)).sum() + (T(cot[2]) * ugp.reshape(B)).sum() + (T(cot[3]) * uob.reshape(B)).sum()
-      gr = dict(zip(L.keys(), torch.autograd.grad(loss, list(L.values()), allow_unused=True)))
-      for key in ('th', 'start', 'goal', 'sdf', 'eps'):
-        if g_e[key] is None or (key == 'sdf' and io == 'f32'): continue
-        a_ = g_e[key]
-        if key == 'sdf' and shared: a_ = a_.sum(0, keepdims=True)
-        b_ = gr[key].numpy().reshape(a_.shape)
-        eb = np.abs(a_ - b_).max() / max(np.abs(b_).max(), np.abs(gr['th'].numpy()).max() if key == 'sdf' else 0.0, 1e-300)
-        assert eb < (1e-8 if io == 'f64' else 1e-4), (tag, 'eval backward', key, eb)
+    long_checks(be, io, p, th, start, goal, sdf, qc, ow, eps, q_full, rs, 'long: dof %d n %d %s %s' % (dof, n, cov, io))
+
+
+def long_checks(be, io, p, th, start, goal, sdf, qc, ow, eps, q_full, rs, tag):
+  """What case_long_trajectories checks on one set of (already rounded) inputs -- every entry point of the loop kernels; rs draws the cotangents."""
+  from oracle import blocktri as BT, autograd_torch as AT
+  B, n, d = th.shape
+  r = lambda a: None if a is None else rnd(a, io)
+  kwc = dict(qc=qc, ow=ow, eps=eps, q_full=q_full)
+  tol = TOL[io] * (10 if n > 512 else 1)               # cond(Lambda) grows with n (dt^-3 in Q^-1): the fp64 oracles themselves differ by that much
+  # ---- one step, every trajectory against the block-tridiagonal C oracle
+  dth, err, eex, info = be.step(p, th, start, goal, sdf, io=io, **kwc)
+  c_dth, c_err, c_eex, c_info = BT.gn_step(p, th, start, goal, sdf, **kwc)
+  assert not info.any() and not c_info.any() and np.all(np.isfinite(dth)), tag
+  assert rel_err_per_traj(dth, c_dth) < tol, (tag, 'step', rel_err_per_traj(dth, c_dth))
+  assert rel_err(err, c_err) < TOL_ERR[io] and rel_err(eex, c_eex) < TOL_ERR[io], (tag, 'errors of the step')
+  # ---- the error evaluation against the step's own errors and the oracle's unweighted errors
+  e = be.eval_errors(p, th, start, goal, sdf, io=io, **kwc)
+  assert rel_err(e[0], c_err) < TOL_ERR[io] and rel_err(e[1], c_eex) < TOL_ERR[io], (tag, 'eval_errors')
+  sdfB = np.broadcast_to(sdf, (B,) + sdf.shape[1:])
+  import torch
+  usg, ugp, uob = AT.unweighted_errors(*[torch.from_numpy(np.array(a, dtype=np.float64)) for a in
+                                         (th, start, goal, sdfB, (p.static_covs(B)[2] if eps is None else eps.reshape(B, n, 1, 1)))], p)
+  for got, want, name in ((e[2], usg, 'sg'), (e[3], ugp, 'gp'), (e[4], uob, 'obs')):
+    assert rel_err(got, want.numpy().reshape(-1)) < TOL_ERR[io] * 10, (tag, 'unweighted ' + name, rel_err(got, want.numpy().reshape(-1)))
+  # ---- the fused loop equals chained steps (3 iterations; fp64 I/O: chained fp32 steps would round the state in between)
+  if io == 'f64' and n <= 512:
+    tho, its, eh, eeh, ef, sinfo = be.solve(p, th, start, goal, sdf, 3, 0.0, io=io, **kwc)
+    cur = th.copy()
+    for k in range(3):
+      d_k, e_k, x_k, i_k = be.step(p, cur, start, goal, sdf, io=io, **kwc)
+      assert rel_err(eh[:, k], e_k) < 1e-10 and rel_err(eeh[:, k], x_k) < 1e-10, (tag, 'history', k)
+      cur = cur + d_k
+    assert np.all(its == 3) and not sinfo.any() and rel_err(tho, cur) < 1e-9, (tag, 'fused loop', rel_err(tho, cur))
+    assert rel_err(ef, be.eval_errors(p, cur, start, goal, sdf, io=io, **kwc)[0]) < 1e-9, (tag, 'err_final')
+  # ---- backward of the step against torch autograd over the dense restatement (N = n d up to 1 920 here)
+  if n <= 320:
+    gbar = r(rs.randn(B, n, d)); gext = r(rs.randn(B))
+    shared = sdf.shape[0] == 1
+    g_h = be.backward(p, th, start, goal, sdf, rnd(dth, io), gbar, gext, io=io, sdf_copies=(16 if shared else 1), **kwc)
+    g_o = AT.step_gradients(p, th, start, goal, sdf, gbar, gext, **kwc)
+    for key in ('th', 'start', 'goal', 'sdf', 'qc', 'ow', 'eps'):
+      if g_h[key] is None or (key == 'sdf' and io == 'f32'): continue
+      a_ = g_h[key]
+      if key == 'sdf' and shared: a_ = a_.sum(0, keepdims=True)
+      b_ = g_o[key].reshape(a_.shape)
+      eb = np.abs(a_ - b_).max() / max(np.abs(b_).max(), np.abs(g_o['th']).max() if key == 'sdf' else 0.0, 1e-300)
+      assert eb < (1e-6 if io == 'f64' else 2e-3), (tag, 'backward', key, eb)
+    # ... and of the error evaluation (unweighted errors + err_ext), against autograd over the same restatement
+    cot = [r(rs.randn(B)) for _ in range(4)]
+    g_e = be.eval_backward(p, th, start, goal, sdf, g_err_ext=cot[0], g_unw_sg=cot[1], g_unw_gp=cot[2], g_unw_obs=cot[3], eps=eps, io=io,
+                           sdf_copies=(16 if shared else 1))
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+    L = dict(th=T(th), start=T(start), goal=T(goal), sdf=T(sdf), eps=T(p.static_covs(B)[2] if eps is None else eps.reshape(B, n, 1, 1)))
+    for v in L.values(): v.requires_grad_(True)
+    sB = L['sdf'].expand(B, *L['sdf'].shape[1:]) if shared else L['sdf']
+    sq, so, se = p.static_covs(B)
+    _, _, eext = AT.plan_layer_forward(L['th'], L['start'], L['goal'], sB, T(sq), T(so), L['eps'], p)
+    usg, ugp, uob = AT.unweighted_errors(L['th'], L['start'], L['goal'], sB, L['eps'], p)
+    loss = (T(cot[0]) * eext.reshape(B)).sum() + (T(cot[1]) * usg.reshape(B)).sum() + (T(cot[2]) * ugp.reshape(B)).sum() + (T(cot[3]) * uob.reshape(B)).sum()
+    gr = dict(zip(L.keys(), torch.autograd.grad(loss, list(L.values()), allow_unused=True)))
+    for key in ('th', 'start', 'goal', 'sdf', 'eps'):
+      if g_e[key] is None or (key == 'sdf' and io == 'f32'): continue
+      a_ = g_e[key]
+      if key == 'sdf' and shared: a_ = a_.sum(0, keepdims=True)
+      b_ = gr[key].numpy().reshape(a_.shape)
+      eb = np.abs(a_ - b_).max() / max(np.abs(b_).max(), np.abs(gr['th'].numpy()).max() if key == 'sdf' else 0.0, 1e-300)
+      assert eb < (1e-8 if io == 'f64' else 1e-4), (tag, 'eval backward', key, eb)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Away from the default configuration constants.  Every other case runs at OracleParams()'s x_lims = y_lims = (-5, 5), total_time_sec = 10, K_s = K_g = 0.01,
+# cost_sigma = 0.01, radius = 0.4, where K_s and K_g, the x and the y limits, their lower and (negated) upper ends and the two spans cannot be told apart and only one
+# dt enters the host-made constant tables.  ND moves every constant; tests/test_config_constants.py guards that each of them moves the oracle's answer on these
+# inputs by 100 x the fp32 parity bound and more.
+ND = dict(total_time_sec=7.0, K_s=0.02, K_g=0.005, cost_sigma=0.03, epsilon_dist=0.25, radius=0.3, reg=0.05, x_lims=(-3.0, 8.0), y_lims=(-4.0, 6.0))
+ND_VEL = dict(use_vel_limits=True, K_v=0.02, v_x=0.6, v_y=0.9)
+ND_DYN = dict(non_holonomic=True, K_d=0.05)
+ND_DEFAULT = dict(total_time_sec=10.0, K_s=0.01, K_g=0.01, cost_sigma=0.01, epsilon_dist=0.4, radius=0.4, reg=0.1, K_v=0.01, v_x=1.0, v_y=1.0, K_d=0.01)
+ND_HW = (33, 37)                   # non-square, W = 37: res = 11 / 37 is no power of two
+ND_CIRCLES = ((0.5, 1.0, 1.2), (4.5, -1.0, 1.0), (6.0, 3.0, 0.8))
+# (start x, y, goal x, y): trajectory 3 leaves the grid (x > 8) through the clamped band, trajectory 4 starts in the band
+ND_ENDS = np.array([[-2.0, -1.0, 7.0, 2.5], [7.0, -3.0, -2.0, 3.0], [-1.0, 3.0, 7.5, -2.0], [2.0, -3.5, 9.0, 5.5], [1.0, 5.5, 6.5, -3.0]])
+ND_QC = {'cI': lambda dof: 2.5 * np.eye(dof), 'diag': lambda dof: np.diag([0.7, 2.5, 1.6][:dof]),
+         'full': lambda dof: np.array([[1.3, 0.4, -0.1], [0.4, 0.9, 0.3], [-0.1, 0.3, 2.0]])[:dof, :dof]}
+
+
+def nd_grid(H=ND_HW[0], W=ND_HW[1], x_lims=ND['x_lims'], y_lims=ND['y_lims'], circles=ND_CIRCLES):
+  """(1,1,H,W) union-of-circles field laid out in PIXEL space the way the lookup reads it (sdf_utils.py:57-62): column px holds x = x_lims[0] + px res, row py holds
+  y = -y_lims[0] - py res with res = x-span / W.  With unsymmetric y limits that is the mirror image of the limits: here rows cover y in (-5.8, 4], the workspace's
+  y in (4, 6] lies above row 0 (both taps clamp to it, the weights cancel: distance 0, Jacobian 0) and the rows below y = -4 lie outside the limits."""
+  res = (x_lims[1] - x_lims[0]) / W
+  x = (np.arange(W) + x_lims[0] / res) * res
+  y = (-y_lims[0] / res - np.arange(H)) * res
+  yy, xx = np.meshgrid(y, x, indexing='ij')
+  return np.min([np.sqrt((xx - cx) ** 2 + (yy - cy) ** 2) - r for cx, cy, r in circles], axis=0)[None, None]
+
+
+def nd_params(dof, n, **extra):
+  kw = dict(ND)
+  if dof == 3: kw.update(ND_DYN)
+  kw.update(extra)
+  return O.OracleParams(dof=dof, total_time_step=n - 1, **kw)
+
+
+class NdInputs(object):
+  pass
+
+
+def nondefault_inputs(dof, n, B, cov, io):
+  """The inputs of every check at ND: th (B,n,d), start, goal, one shared ND_HW grid, and for cov 'perstate' / 'qfull' / 'scalar' the covariance tensors
+  (qc (B,n-1,dof,dof) / (B,n-1,d,d) / (B,n-1); ow, eps (B,n)), all rounded to the I/O type.  Trajectory b is the same whatever B is.  By construction -- and
+  asserted here -- every trajectory has at least 3 hinge-active interior states under the static epsilon, trajectory 3 leaves the grid and trajectories 3 and 4
+  cross the clamped band above row 0."""
+  assert 1 <= B <= len(ND_ENDS) and cov in ('static', 'perstate', 'qfull', 'scalar')
+  E, d = len(ND_ENDS), 2 * dof
+  rs = np.random.RandomState(1000 * dof + n)
+  start = np.zeros((E, 1, d)); goal = np.zeros((E, 1, d))
+  start[:, 0, :2] = ND_ENDS[:, :2]; goal[:, 0, :2] = ND_ENDS[:, 2:]
+  if dof == 3: goal[:, 0, 2] = rs.uniform(-2, 2, E)
+  th = O.straight_line_trajb(start[:, :, :dof], goal[:, :, :dof], ND['total_time_sec'], n - 1, dof) + rs.randn(E, n, d) * 0.05
+  x = NdInputs()
+  x.qc = x.ow = x.eps = None; x.q_full = False
+  if cov != 'static':
+    x.ow = rs.uniform(50, 2e4, (E, n)); x.eps = rs.uniform(0.1, 0.6, (E, n))
+    if cov == 'perstate':
+      A = rs.randn(E, n - 1, dof, dof) * 0.2; x.qc = np.eye(dof) + A @ np.swapaxes(A, -1, -2)
+    elif cov == 'qfull':
+      A = rs.randn(E, n - 1, d, d) * 0.2; x.qc = (np.eye(d) + A @ np.swapaxes(A, -1, -2)) * 1.5; x.q_full = True
+    else:
+      x.qc = rs.uniform(0.3, 3.0, (E, n - 1)) ** 2
+  r = lambda a: None if a is None else rnd(a[:B], io)
+  x.th, x.start, x.goal, x.qc, x.ow, x.eps = r(th), r(start), r(goal), r(x.qc), r(x.ow), r(x.eps)
+  x.sdf = rnd(nd_grid(), io)
+  x.B, x.n, x.dof, x.cov = B, n, dof, cov
+  p = nd_params(dof, n)
+  res = (p.x_lims[1] - p.x_lims[0]) / ND_HW[1]
+  dist = O.bilinear_interpolate(np.broadcast_to(x.sdf[:, 0], (B,) + ND_HW), x.th[:, :, :2], res, p.x_lims, p.y_lims)[0].reshape(B, n)
+  x.active = dist <= p.epsilon_dist + p.radius
+  assert x.active[:, 1:-1].sum(1).min() >= 3, x.active[:, 1:-1].sum(1)
+  band = (x.th[:, :, 1] > -p.y_lims[0]) & (x.th[:, :, 1] <= p.y_lims[1])
+  if B > 3: assert (x.th[3, :, 0] > p.x_lims[1]).any() and band[3].any()
+  if B > 4: assert band[4].any()
+  return x
+
+
+# (family, dofs, forced shape, n, covariances, extra parameters by dof, the static kernel variant expected (dgp_step_kernel_variant), checks)
+_ALL = ('solve', 'errors', 'backward', 'eval_backward')
+ND_ROWS = [
+    ('woodbury exact', (2, 3), '16,4', 64, 'static', lambda dof: dict(Q_c_inv=ND_QC['cI'](dof)), 3, _ALL + ('step_errors',)),
+    ('woodbury ragged', (2, 3), '16,4', 61, 'static', lambda dof: dict(Q_c_inv=ND_QC['cI'](dof)), 4, _ALL + ('step_errors',)),
+    ('woodbury ragged', (2, 3), '16,4', 13, 'static', lambda dof: dict(Q_c_inv=ND_QC['cI'](dof)), 4, _ALL + ('chain',)),
+    ('static velocity limits', (2,), '16,4', 61, 'static', lambda dof: dict(ND_VEL), 1, _ALL + ('step_errors', 'chain')),
+    ('static diagonal', (3,), '16,4', 61, 'static', lambda dof: dict(Q_c_inv=ND_QC['diag'](dof)), 1, _ALL + ('step_errors', 'chain')),
+    ('general static', (2, 3), '16,1', 13, 'static', lambda dof: dict(Q_c_inv=ND_QC['full'](dof)), 0, _ALL + ('chain',)),
+    ('kronecker per-state', (2, 3), '16,1', 13, 'perstate', lambda dof: {}, None, _ALL),
+    ('kronecker per-state', (2, 3), '16,4', 61, 'perstate', lambda dof: {}, None, _ALL + ('step_errors',)),
+    ('q_full', (2, 3), '16,1', 13, 'qfull', lambda dof: {}, None, _ALL),
+    ('q_full', (2, 3), '16,4', 61, 'qfull', lambda dof: {}, None, _ALL),
+    ('scalar', (2, 3), '16,1', 13, 'scalar', lambda dof: dict(Q_c_inv=ND_QC['cI'](dof)), None, ('backward',)),      # (DGP_QC_SCALAR is a step-only mode)
+    ('scalar', (2, 3), '16,4', 61, 'scalar', lambda dof: dict(Q_c_inv=ND_QC['cI'](dof)), None, ('backward',)),      # (DGP_QC_SCALAR is a step-only mode)
+]
+CHAIN_COV = {'woodbury ragged': 'static', 'static velocity limits': 'static_diag', 'static diagonal': 'static_diag', 'general static': 'static_full'}
+ND_LONG = [(2, 257, 'static', {}), (3, 257, 'perstate', {})]
+
+
+def nd_row(be, io, row, dof, rec, nb=None):
+  """One row of ND_ROWS for one robot.  rec(tag, what, value, bound) notes a figure and whether it is within its bound.  Bounds: the step, the errors and the fused
+  loop as test_hip_every_kernel.py / case_long_trajectories hold them against the C oracle (TOL, TOL_ERR, 1e-7 | 1e-5), the unweighted errors lane_mix.UNW_TOL,
+  gradients against the autograd oracle 1e-6 | 2e-3 (test_hip_every_backward_kernel_vs_autograd_oracle) and 1e-8 | 1e-4 for the error evaluation's
+  (case_long_trajectories), the training iteration lane_mix.TWIN_STEP_TOL / UNW_TOL and 1e-7 (= lane_mix.ERRS_BWD_TOL) | 2e-3 (test_hip_every_step_errors_kernel),
+  the chain lane_mix.CHAIN_TOL | 5e-3 (test_hip_every_chain_backward_kernel)."""
+  import os
+  import harness
+  import lane_mix as LM
+  from dgpmp2_amd import _capi
+  from oracle import blocktri as BT, autograd_torch as AT
+  family, _, shape, n, cov, extra, variant, checks = row
+  os.environ['DGP_FORCE_SHAPE'] = shape
+  lpt = int(shape.split(',')[0])
+  B, d = (64 // lpt + 1 if nb is None else nb), 2 * dof      # one full and one ragged wavefront
+  p = nd_params(dof, n, **extra(dof))
+  x = nondefault_inputs(dof, n, B, cov, io)
+  tag = '%s dof %d shape (%s) n %d %s%s' % (family, dof, shape, n, io, ' tiled' if be.sdf_tiled else '')
+  if variant is not None and not be.sdf_tiled:
+    got = _capi.Solver(harness.config_from_oracle(p, io), api=be.api).step_kernel_variant(B)
+    assert got == variant, (tag, 'kernel variant', got, variant)
+  sh = (B, n, 1, 1)
+  qd = x.qc[:, :, None, None] * p.Q_c_inv if cov == 'scalar' else x.qc      # the blocks s_k Q_c_inv the oracles take
+  okw = dict(qc=qd, ow=None if x.ow is None else x.ow.reshape(sh), eps=None if x.eps is None else x.eps.reshape(sh), q_full=x.q_full)
+  kw = dict(qc=x.qc, ow=x.ow, eps=x.eps, q_full=x.q_full, io=io)
+  a = (p, x.th, x.start, x.goal, x.sdf)
+  f64 = io == 'f64'
+  rs = np.random.RandomState(7 * n + dof)
+  r = lambda v: rnd(v, io)
+  fin = lambda v: np.all(np.isfinite(v))
+  # ---- one step against the C oracle, per trajectory
+  dth, err, eex, info = be.step(*a, **kw)
+  c_dth, c_err, c_eex, c_info = BT.gn_step(*a, **okw)
+  assert not info.any() and not c_info.any() and fin(dth), tag
+  rec(tag, 'step dtheta', rel_err_per_traj(dth, c_dth), TOL[io])
+  rec(tag, 'step err', rel_err(err, c_err), TOL_ERR[io]); rec(tag, 'step err_ext', rel_err(eex, c_eex), TOL_ERR[io])
+  # ---- the fused loop: three iterations == three chained oracle steps
+  if 'solve' in checks:
+    tho, its, eh, eeh, ef, sinfo = be.solve(*a, 3, 0.0, **kw)
+    cur = x.th.copy()
+    for k in range(3): cur = cur + BT.gn_step(p, cur, x.start, x.goal, x.sdf, **okw)[0]
+    assert not sinfo.any() and np.all(its == 3) and fin(tho), (tag, 'fused loop')
+    rec(tag, 'fused loop', rel_err(tho, cur), 1e-7 if f64 else 1e-5)
+  # ---- the error evaluation
+  eps4 = np.full(sh, p.epsilon_dist) if x.eps is None else x.eps.reshape(sh)
+  if 'errors' in checks:
+    e = be.eval_errors(*a, **kw)
+    rec(tag, 'eval err', rel_err(e[0], c_err), TOL_ERR[io]); rec(tag, 'eval err_ext', rel_err(e[1], c_eex), TOL_ERR[io])
+    unw = O.unweighted_errors_batch(x.th, x.start, x.goal, np.broadcast_to(x.sdf, (B,) + x.sdf.shape[1:]), eps4, p)
+    for got, want, name in zip(e[2:], unw, ('sg', 'gp', 'obs')): rec(tag, 'unweighted ' + name, rel_err(got, want.reshape(-1)), LM.UNW_TOL[io])
+  gm = 'dense' if f64 else 'f64'      # fp32 I/O: the grid gradient in float64 grids, as those tests take it
+  bt = LM.Batch()
+  bt.p, bt.th, bt.start, bt.goal, bt.sdf, bt.eps, bt.B, bt.n, bt.lpt, bt.tag, bt.nan_rows = p, x.th, x.start, x.goal, x.sdf, x.eps, B, n, lpt, tag, np.zeros(0, np.int64)
+
+  def grads(what, got, want, bound, keys):
+    for key in keys:
+      if got.get(key) is None or want.get(key) is None: continue
+      g_, w_ = got[key], np.asarray(want[key])
+      if key == 'sdf' and g_.shape[0] != w_.shape[0]: g_ = g_.sum(0, keepdims=True)
+      w_ = w_.reshape(g_.shape)
+      v = np.abs(g_ - w_).max() / max(np.abs(w_).max(), np.abs(want['th']).max() if key == 'sdf' else 0.0, 1e-300) if fin(g_) else np.inf
+      rec(tag, '%s g_%s' % (what, key), v, bound)
+  # ---- backward of the step against torch autograd over the dense restatement
+  if 'backward' in checks:
+    gbar, gext = r(rs.randn(B, n, d)), r(rs.randn(B))
+    g_h = be.backward(*a, r(dth), gbar, gext, sdf_grad=gm, **kw)
+    g_o = AT.step_gradients(*a, gbar, gext, **okw)
+    grads('backward', g_h, g_o, 1e-6 if f64 else 2e-3, ('th', 'start', 'goal', 'sdf', 'qc', 'ow', 'eps'))
+  # ---- backward of the unweighted errors against torch autograd
+  if 'eval_backward' in checks:
+    cs, cg, co = r(rs.randn(B)), r(rs.randn(B)), r(rs.randn(B))
+    g_e = be.eval_backward(*a, None, cs, cg, co, eps=x.eps, io=io, want_sdf=False)
+    grads('eval backward', g_e, LM.unw_autograd(bt, np.arange(B), cs, cg, co), 1e-8 if f64 else 1e-4, ('th', 'start', 'goal') + (('eps',) if x.eps is not None else ()))
+  # ---- the training iteration, as case_step_errors / test_hip_every_step_errors_kernel hold it
+  if 'step_errors' in checks:
+    npdt = np.float64 if f64 else np.float32
+    fw = be.step_errors(*a, **kw)
+    assert not fw[3].any(), (tag, 'step_errors info')
+    for i, name in enumerate(('dtheta', 'err', 'err_ext')): rec(tag, 'step_errors %s vs step' % name, rel_err(fw[i], (dth, err, eex)[i]), LM.TWIN_STEP_TOL[io])
+    th_new = (x.th.astype(npdt) + fw[0].astype(npdt)).astype(np.float64)
+    unw = O.unweighted_errors_batch(th_new, x.start, x.goal, np.broadcast_to(x.sdf, (B,) + x.sdf.shape[1:]), eps4, p)
+    for got, want, name in zip(fw[4:], unw, ('sg', 'gp', 'obs')): rec(tag, 'step_errors unweighted ' + name, rel_err(got, want.reshape(-1)), LM.UNW_TOL[io])
+    gd, ce = r(rs.randn(B, n, d)), r(rs.randn(B))
+    cs, cg, co = r(rs.randn(B)), r(rs.randn(B)), r(rs.randn(B))
+    h1 = be.eval_backward(p, th_new, x.start, x.goal, x.sdf, None, cs, cg, co, eps=x.eps, io=io, want_sdf=False)
+    h2 = be.backward(*a, fw[0], (gd.astype(npdt) + h1['th'].astype(npdt)).astype(np.float64), ce, sdf_grad=gm, **kw)
+    want = dict(th=h2['th'] + h1['th'], start=h2['start'] + h1['start'], goal=h2['goal'] + h1['goal'], qc=h2['qc'], ow=h2['ow'],
+                eps=None if x.eps is None else h2['eps'] + h1['eps'])
+    got = be.step_errors_backward(*a, fw[0], gd, ce, cs, cg, co, sdf_grad='none', **kw)
+    grads('step_errors backward', got, want, LM.ERRS_BWD_TOL if f64 else 2e-3, ('th', 'start', 'goal', 'qc', 'ow', 'eps'))
+  # ---- the traced loop and its backward against single-step backward launches walked through the history
+  if 'chain' in checks:
+    K = 2
+    tho, its, hist = be.solve_traced(*a, K, 0.0, io=io)[:3]
+    assert (its == K).all(), (tag, 'traced loop', its)
+    gb = r(rs.randn(B, n, d))
+    got = be.solve_backward(p, x.start, x.goal, x.sdf, K, hist, tho, its, gb, io=io, sdf_grad=gm)
+    want = LM.chain_walk(be, bt, K, hist, tho, its, gb, io, gm)
+    bound = LM.CHAIN_TOL[CHAIN_COV[family]] if f64 else 5e-3
+    for key in ('th', 'start', 'goal'):
+      w_ = np.asarray(want[key], np.float64).reshape(B, -1)
+      v = np.abs(got[key].reshape(B, -1) - w_).max(1) / np.maximum(np.abs(w_).max(1), 1e-3 * np.abs(w_).max())      # (lane_mix.check_grads' per-trajectory scale)
+      rec(tag, 'chain backward g_' + key, float(v.max()) if fin(got[key]) else np.inf, bound)
+
+
+def nd_fixture_rows(be, g, rec):
+  """the reference's own outputs at ND (tests/golden/g11_config_constants.npz): fp64, the bounds of check_step's golden comparison"""
+  import os
+  n = int(g['n'])
+  os.environ.pop('DGP_FORCE_SHAPE', None)
+  for key, dof, extra, covs in (('static', 2, dict(Q_c_inv=g['Q_c_inv']), False), ('vel', 2, dict(ND_VEL, Q_c_inv=g['Q_c_inv']), False), ('cov', 2, dict(Q_c_inv=g['Q_c_inv']), True),
+                                ('xyh', 3, dict(Q_c_inv=g['xyh_Q_c_inv']), False)):
+    p = nd_params(dof, n, **extra)
+    pre = 'xyh_' if dof == 3 else ''
+    B = g[pre + 'th'].shape[0]
+    kw = dict(qc=g['qc'], ow=g['ow'].reshape(B, n), eps=g['eps'].reshape(B, n)) if covs else {}
+    dth, err, eex, info = be.step(p, g[pre + 'th'], g[pre + 'start'], g[pre + 'goal'], g['sdf'], io='f64', **kw)
+    tag = 'fixture g11 %s%s' % (key, ' tiled' if be.sdf_tiled else '')
+    assert not info.any(), tag
+    rec(tag, 'dtheta', rel_err(dth, g[key + '_dth']), TOL['f64']); rec(tag, 'dtheta per trajectory', rel_err_per_traj(dth, g[key + '_dth']), TOL['f64'])
+    rec(tag, 'err', rel_err(err, g[key + '_err'].reshape(-1)), TOL_ERR['f64'])
+    if key + '_errext' in g: rec(tag, 'err_ext', rel_err(eex, g[key + '_errext'].reshape(-1)), TOL_ERR['f64'])
+
+
+class NdReport(object):
+  """Collects (tag, what, value, bound) of every comparison; worst(): per family and quantity the largest value next to its bound."""
+
+  def __init__(self, verbose=True): self.rows, self.verbose = [], verbose
+
+  def __call__(self, tag, what, value, bound):
+    self.rows.append((tag, what, float(value), float(bound)))
+    if self.verbose: print('config_constants: %-58s %-34s %.3g (bound %.1g)%s' % (tag, what, value, bound, '' if value < bound else '   <-- EXCEEDED'), flush=True)
+
+  def failures(self): return [row for row in self.rows if not row[2] < row[3]]
+
+
+def case_config_constants(be, golden, io, rows=None, dofs=(2, 3), long=True, fixture=True, nb=None):
+  """Every entry point and kernel family at the constants ND (nothing equal to its default, K_s != K_g, unsymmetric and unequal x and y limits, another horizon), on the
+  smallest configurations that reach each constant-dependent path: see ND_ROWS.  Every figure is printed before the bounds are asserted together.
+
+  Worst figures on the MI355X, fp64 | fp32 I/O, both robots and both grid layouts (bounds: nd_row's docstring):
+    family                   dtheta (1e-9 | 1e-5)   errors (1e-11 | 2e-6)   fused loop (1e-7 | 1e-5)   step gradients (1e-6 | 2e-3)   chain (CHAIN_TOL | 5e-3)
+    Woodbury exact           2.7e-12 | 5.2e-8       4.4e-16 | 2.7e-8        1.2e-11 | 5.3e-8           2.0e-12 | 1.8e-7               -
+    Woodbury ragged          5.0e-12 | 4.8e-8       4.9e-16 | 4.0e-8        1.5e-11 | 5.2e-8           6.8e-12 | 1.1e-7               4.3e-15 | 6.4e-5
+    static, velocity limits  4.0e-13 | 4.5e-8       6.0e-16 | 2.6e-8        7.9e-14 | 5.3e-8           4.3e-13 | 6.4e-8               0 | 1.9e-6
+    static, diagonal (d = 6) 1.5e-12 | 4.2e-8       1.7e-16 | 3.5e-8        3.3e-12 | 4.8e-8           1.1e-12 | 1.7e-7               0 | 5.2e-6
+    general static           4.4e-14 | 4.5e-8       1.9e-16 | 3.9e-8        1.5e-13 | 4.2e-8           4.9e-15 | 6.4e-8               9.0e-13 | 3.7e-5
+    Kronecker per-state      1.1e-12 | 5.0e-8       5.0e-16 | 5.2e-8        2.5e-12 | 5.1e-8           3.4e-12 | 4.1e-6               -
+    q_full                   1.0e-10 | 4.8e-8       5.0e-16 | 5.2e-8        2.4e-11 | 5.3e-8           5.5e-10 | 7.1e-5               -
+    scalar                   5.2e-12 | 5.1e-8       4.7e-16 | 4.0e-8        -                          7.0e-12 | 1.7e-6               -
+  unweighted errors 1.3e-15 | 5.3e-8 (1e-11 | 3e-5), their gradients 4.9e-17 | 5.0e-8 (1e-8 | 1e-4), the training iteration against the step 0 | 0 and its backward
+  against its halves 3.3e-14 | 7.9e-8 (1e-7 | 2e-3), the reference's rows of g11 3.2e-13 in dtheta and 3.7e-16 in the errors."""
+  import os
+  saved = os.environ.get('DGP_FORCE_SHAPE')
+  rec = NdReport()
+  try:
+    for row in (ND_ROWS if rows is None else rows):
+      for dof in row[1]:
+        if dof in dofs: nd_row(be, io, row, dof, rec, nb)
+    os.environ.pop('DGP_FORCE_SHAPE', None)
+    if long and not be.sdf_tiled:      # (the loop kernels take row-major grids only)
+      for dof, n, cov, extra in ND_LONG:
+        x = nondefault_inputs(dof, n, 2, cov, io)
+        long_checks(be, io, nd_params(dof, n, **extra), x.th, x.start, x.goal, x.sdf, x.qc, x.ow, x.eps, x.q_full, np.random.RandomState(n + dof),
+                    'config constants, loop kernels: dof %d n %d %s %s' % (dof, n, cov, io))
+    if fixture and io == 'f64': nd_fixture_rows(be, golden('g11_config_constants'), rec)
+  finally:
+    if saved is None: os.environ.pop('DGP_FORCE_SHAPE', None)
+    else: os.environ['DGP_FORCE_SHAPE'] = saved
+  bad = rec.failures()
+  assert not bad, '%d of %d figures beyond their bound:\n' % (len(bad), len(rec.rows)) + '\n'.join('%s: %s %.3g >= %.1g' % b_ for b_ in bad)
+  return rec
+
+
+ALL_CASES.append(case_config_constants)

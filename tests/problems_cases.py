@@ -80,3 +80,45 @@ def branch_counts(env, diag, draws, info):
 def check_branches(c):
   assert c['first_draw'] > 0 and c['beyond_group'] > 0 and c['both_caps'] > 0 and c['near_tries'] > 0, c
   assert min(c['diagonal_kept']) > 0 and min(c['diagonal_replaced']) > 0, c
+
+
+# ---- away from the default limits and horizon: x and y limits that differ from each other and are not symmetric, total_time_sec = 7 ------------------------------
+# res = 10 / 20 = 0.5; rows follow py = -y_lims[0] / res - y / res = 12 - 2 y (env_2d.py:60-62), so the box y in [-6, 2] lies in rows 8 ... 24 of 26 and rows 0 ... 7 are
+# never read (y > 2 is outside the limits); columns 0 ... 20 hold x in [-3, 7].  The fields keep the kinds and the branch each one forces.
+ND_X, ND_Y, ND_T_SEC, ND_HW, ND_N = (-3.0, 7.0), (-6.0, 2.0), 7.0, (26, 20), 16
+
+
+def fields_nd():
+  """(5, 26, 20) float64"""
+  f = np.full((5,) + ND_HW, -1.0)
+  f[EMPTY] = 3.0
+  f[CLUTTER, 10:13, 2:5] = 3.0
+  f[CLUTTER, 20:23, 15:18] = 3.0
+  f[POCKET, 14:19, 8:13] = 3.0
+  f[CORNERS] = 3.0
+  f[CORNERS, 19:, :5] = -1.0
+  f[CORNERS, 19:, 15:] = -1.0
+  return f
+
+
+def params_nd(x_lims=ND_X, y_lims=ND_Y):
+  return PO.Params(CLEARANCE, x_lims=x_lims, y_lims=y_lims, max_draws=MAX_DRAWS, corner_inset=INSET, total_time_sec=ND_T_SEC)
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_nd(B=B_MAIN, seed=7, x_lims=ND_X, y_lims=ND_Y):
+  """mixed() on fields_nd() at the limits given (default: ND_X, ND_Y)"""
+  f = fields_nd()
+  env, diag = layout(B)
+  out = PO.sample_problems(f, params_nd(x_lims, y_lims), B, seed, 0, env, diag)
+  for a in (f, env, diag) + out: a.setflags(write=False)
+  return f, env, diag, out
+
+
+@functools.lru_cache(maxsize=None)
+def shared_nd(B=B_MAIN, seed=11):
+  f = fields_nd()[CORNERS:CORNERS + 1]
+  _, diag = layout(B)
+  out = PO.sample_problems(f, params_nd(), B, seed, 0, None, diag)
+  for a in (f, diag) + out: a.setflags(write=False)
+  return f, None, diag, out

@@ -42,6 +42,15 @@ def test_hip_tiled_grids(golden, io):
 
 
 @pytest.mark.parametrize('io', ['f64', 'f32'])
+def test_hip_config_constants_tiled_grids(golden, io):
+  """parity_cases.case_config_constants -- every kernel family away from the default limits, horizon and factor weights -- once more with the 33 x 37 grid stored as
+  4 x 4 tiles (padding cells in the last tile row and column); the tiled twins exist for the shapes (16,4) and (32,4), which a forced (16,1) then gives way to, and not for
+  the loop kernels, whose rows the case leaves out."""
+  bt = harness.Backend('hip'); bt.sdf_tiled = True
+  PC.case_config_constants(bt, golden, io)
+
+
+@pytest.mark.parametrize('io', ['f64', 'f32'])
 def test_hip_c2_tiled_equals_row_major(io):
   """BASELINE config 2's shape with 1024 DISTINCT grids: the step on the tiled grids equals the step on the row-major ones to rounding (the same taps read from
   another address -- but by the tiled translation units, a separate compilation of the same source whose FMA contraction may differ), and so does the per-sample

@@ -26,14 +26,14 @@ NP_IO = {'f64': np.float64, 'f32': np.float32}
 T_IO = {'f64': torch.float64, 'f32': torch.float32}
 
 
-def _cfg(n, io):
-  return _capi.make_config(num_states=n, dof=2, io_dtype=_capi.DGP_F64 if io == 'f64' else _capi.DGP_F32, total_time_sec=PCS.T_SEC, x_lims=(-5, 5), y_lims=(-5, 5),
+def _cfg(n, io, x_lims=(-5, 5), y_lims=(-5, 5), t_sec=PCS.T_SEC):
+  return _capi.make_config(num_states=n, dof=2, io_dtype=_capi.DGP_F64 if io == 'f64' else _capi.DGP_F32, total_time_sec=t_sec, x_lims=x_lims, y_lims=y_lims,
                            K_s=0.01, K_g=0.01, reg=0.1, sphere_radius=0.4, Q_c_inv=[[1, 0], [0, 1]], cost_sigma=0.01, epsilon_dist=0.4)
 
 
-def run(n, io, grids, B, env_index=None, diagonal=None, seed=0, first_problem=0, tiled=False):
-  """dgp_sample_problems through the ctypes binding -> (start, goal, th_init, draws, info) as numpy arrays; grids (E, H, W), E = 1: shared"""
-  s = _capi.Solver(_cfg(n, io))
+def run(n, io, grids, B, env_index=None, diagonal=None, seed=0, first_problem=0, tiled=False, **cfg):
+  """dgp_sample_problems through the ctypes binding -> (start, goal, th_init, draws, info) as numpy arrays; grids (E, H, W), E = 1: shared; cfg: _cfg's limits and horizon"""
+  s = _capi.Solver(_cfg(n, io, **cfg))
   E, H, W = grids.shape
   g4 = np.ascontiguousarray(grids[:, None]).astype(NP_IO[io])
   if tiled:
@@ -59,10 +59,10 @@ def run(n, io, grids, B, env_index=None, diagonal=None, seed=0, first_problem=0,
   return tuple(t.cpu().numpy() for t in (start, goal, th, draws, info))
 
 
-def assert_equals_oracle(got, want, n, io, what):
+def assert_equals_oracle(got, want, n, io, what, t_sec=PCS.T_SEC):
   start, goal, th, draws, info = got
   w_start, w_goal, w_draws, w_info = want
-  w_th = PO.th_init_of(w_start, w_goal, n, PCS.T_SEC)
+  w_th = PO.th_init_of(w_start, w_goal, n, t_sec)
   r = lambda a: a.astype(NP_IO[io])      # the oracle's fp64 result, rounded once
   for name, g, w in (('info', info, w_info), ('draws', draws, w_draws), ('start', start, r(w_start)), ('goal', goal, r(w_goal)), ('th_init', th, r(w_th))):
     assert g.dtype == w.dtype and g.shape == w.shape, (what, name)
@@ -88,6 +88,26 @@ def test_bit_exact_against_the_oracle(n, io, tiled, sharing):
     seed = 11
   got = run(n, io, f, B, env, diag, seed=seed, tiled=tiled)
   assert_equals_oracle(got, want, n, io, 'n %d %s %s %s' % (n, io, 'tiled' if tiled else 'rowmajor', sharing))
+
+
+@pytest.mark.parametrize('sharing', ['env_index', 'shared'])
+@pytest.mark.parametrize('tiled', [False, True], ids=['rowmajor', 'tiled'])
+@pytest.mark.parametrize('io', ['f64', 'f32'])
+def test_bit_exact_against_the_oracle_at_other_limits(io, tiled, sharing):
+  """x_lims = (-3, 7), y_lims = (-6, 2), total_time_sec = 7 on 26 x 20 grids (problems_cases.fields_nd): the box's bounds lbx / lby / ubx / uby, the pixel origins of x and
+  y, the four limit tests and the corners of the diagonals all differ from one another and from the default's; tests/test_config_constants.py holds that each limit, and
+  an x / y swap, changes every problem of this batch.  Bit-exact like the default parametrisation above."""
+  n, B = PCS.ND_N, PCS.B_MAIN
+  if sharing == 'env_index':
+    f, env, diag, want = PCS.mixed_nd()
+    PCS.check_branches(PCS.branch_counts(env, diag, want[2], want[3]))
+    seed = 7
+  else:
+    f, env, diag, want = PCS.shared_nd()
+    assert ((want[3] & 8) != 0).sum() > 0 and (diag < 0).sum() > 0
+    seed = 11
+  got = run(n, io, f, B, env, diag, seed=seed, tiled=tiled, x_lims=PCS.ND_X, y_lims=PCS.ND_Y, t_sec=PCS.ND_T_SEC)
+  assert_equals_oracle(got, want, n, io, 'other limits %s %s %s' % (io, 'tiled' if tiled else 'rowmajor', sharing), t_sec=PCS.ND_T_SEC)
 
 
 def _same(a, b):
@@ -144,15 +164,15 @@ def test_optional_outputs_may_be_null_and_max_draws_of_one():
 
 # ---- the Python front end ---------------------------------------------------------------------------------------------------------------------------------------
 
-def _planner(n, max_iters=10):
+def _planner(n, max_iters=10, x_lims=(-5.0, 5.0), y_lims=(-5.0, 5.0), t_sec=PCS.T_SEC):
   from dgpmp2_amd.gpmp2 import DiffGPMP2Planner
   from dgpmp2_amd.robot_models import PointRobot2D
   t = lambda v: torch.tensor(v, dtype=torch.float64)
   gp = {'Q_c_inv': torch.eye(2, dtype=torch.float64), 'K_s': t(0.01), 'K_g': t(0.01)}
   ob = {'cost_sigma': t(0.01), 'epsilon_dist': t(0.4)}
-  pp = {'dof': 2, 'state_dim': 4, 'total_time_sec': PCS.T_SEC, 'total_time_step': n - 1}
+  pp = {'dof': 2, 'state_dim': 4, 'total_time_sec': t_sec, 'total_time_step': n - 1}
   op = {'method': 'gauss_newton', 'reg': 0.1, 'plan_time': float('inf'), 'max_iters': max_iters, 'tol_err': 1e-3, 'tol_delta': 1e-4}
-  env = {'x_lims': [-5.0, 5.0], 'y_lims': [-5.0, 5.0]}
+  env = {'x_lims': list(x_lims), 'y_lims': list(y_lims)}
   return DiffGPMP2Planner(gp, ob, pp, op, env, PointRobot2D(t(0.4), 1, n, use_cuda=True), batch_size=1, use_cuda=True)
 
 
@@ -181,6 +201,20 @@ def test_front_end_equals_the_oracle_and_takes_tiled_grids():
     sample_problems(planner, sdfb, env_index=ei + 1, seed=7)
   with pytest.raises(RuntimeError, match='CUDA/ROCm'):
     sample_problems(planner, sdfb.cpu(), env_index=ei)
+
+
+def test_front_end_at_other_limits():
+  """sample_problems(planner, ...) on a planner built with x_lims = (-3, 7), y_lims = (-6, 2), total_time_sec = 7: limits and horizon reach the kernel from the planner's
+  dictionaries, each in its own place"""
+  from dgpmp2_amd.datasets.problem_generation import sample_problems
+  n = PCS.ND_N
+  planner = _planner(n, x_lims=PCS.ND_X, y_lims=PCS.ND_Y, t_sec=PCS.ND_T_SEC)
+  f, env, diag, want = PCS.mixed_nd()
+  sdfb = torch.from_numpy(f[:, None].copy()).to(DEV)
+  ei, dg = torch.from_numpy(env.copy()).to(DEV), torch.from_numpy(diag.copy()).to(DEV)
+  startb, goalb, thb, info = sample_problems(planner, sdfb, env_index=ei, seed=7, diagonal=dg, max_draws=PCS.MAX_DRAWS, corner_inset=PCS.INSET)
+  got = tuple(t.cpu().numpy() for t in (startb, goalb, thb, info.draws, info.flags))
+  assert_equals_oracle(got, want, n, 'f64', 'front end, other limits', t_sec=PCS.ND_T_SEC)
 
 
 def test_capture_and_replay():

@@ -61,6 +61,18 @@ def test_emul_raw_squared_covariances(be, golden): PC.case_raw_squared_covarianc
 def test_emul_raw_squared_covariances_f32(be, golden): PC.case_raw_squared_covariances(be, golden, 'f32')
 
 
+
+# away from the default configuration constants (parity_cases.ND), trimmed: the rows of the forced shapes (16,4) with n = 64 and n = 13 and (16,1) with n = 13, two
+# trajectories, fp64 -- the step, the fused loop, the errors, every backward against the C and the autograd oracles -- then the reference's own rows of g11; one fp32 row
+_ND_EMUL = [i for i, r in enumerate(PC.ND_ROWS) if (r[2], r[3]) in (('16,4', 64), ('16,4', 13), ('16,1', 13))]
+
+
+@pytest.mark.parametrize('i', _ND_EMUL, ids=lambda i: '%s-%s-n%d' % (PC.ND_ROWS[i][0].replace(' ', '_'), PC.ND_ROWS[i][2].replace(',', 'x'), PC.ND_ROWS[i][3]))
+def test_emul_config_constants(be, golden, i): PC.case_config_constants(be, golden, 'f64', rows=[PC.ND_ROWS[i]], long=False, fixture=False, nb=2)
+def test_emul_config_constants_fixture_rows(be, golden): PC.case_config_constants(be, golden, 'f64', rows=[], long=False)
+def test_emul_config_constants_f32(be, golden): PC.case_config_constants(be, golden, 'f32', rows=[PC.ND_ROWS[2]], dofs=(2,), long=False, nb=2)
+
+
 # ---- launch shapes: LPT lanes per trajectory x C states per lane (local block elimination + PCR over the lanes)
 import os
 import numpy as np

@@ -1110,3 +1110,59 @@ def test_forward_with_grad_and_a_non_diagonal_qc_is_two_launches(golden):
   gr = torch.autograd.grad((T(g['gbar']) * thf).sum(), L)
   for got, key in zip(gr, ('g_th0', 'g_sdf', 'g_start', 'g_goal')):
     assert rel_err(got.cpu().numpy(), g[key]) < 5e-8, (key, rel_err(got.cpu().numpy(), g[key]))
+
+
+# ---- away from the default constants: the reference's own rows at parity_cases.ND (tests/golden/g11_config_constants.npz) ------------------------------------------
+def _nd_planner(g, B, dof=2, **planner_extra):
+  import parity_cases as PC
+  from dgpmp2_amd.robot_models import PointRobot2D, PointRobotXYH
+  from dgpmp2_amd.gpmp2 import DiffGPMP2Planner
+  n = int(g['n'])
+  t = lambda v: torch.tensor(v, dtype=torch.float64)
+  gp = {'Q_c_inv': t(g['Q_c_inv'] if dof == 2 else g['xyh_Q_c_inv']), 'K_s': t(PC.ND['K_s']), 'K_g': t(PC.ND['K_g']), 'K_v': t(PC.ND_VEL['K_v']),
+        'v_x': [PC.ND_VEL['v_x']], 'v_y': [PC.ND_VEL['v_y']], 'K_d': t(PC.ND_DYN['K_d'])}
+  ob = {'cost_sigma': t(PC.ND['cost_sigma']), 'epsilon_dist': t(PC.ND['epsilon_dist'])}
+  pp = dict({'dof': dof, 'state_dim': 2 * dof, 'total_time_sec': PC.ND['total_time_sec'], 'total_time_step': n - 1}, **planner_extra)
+  op = {'method': 'gauss_newton', 'reg': PC.ND['reg'], 'plan_time': float('inf'), 'max_iters': 10, 'tol_err': 1e-3, 'tol_delta': 1e-4}
+  ev = {'x_lims': list(PC.ND['x_lims']), 'y_lims': list(PC.ND['y_lims'])}
+  r = t(PC.ND['radius'])
+  robot = PointRobot2D(r, B, n, use_cuda=True) if dof == 2 else PointRobotXYH(r, use_cuda=True, batch_size=B, num_traj_states=n)
+  return DiffGPMP2Planner(gp, ob, pp, op, ev, robot, batch_size=B, use_cuda=True)
+
+
+def test_step_and_autograd_match_the_reference_at_other_constants(golden):
+  """A DiffGPMP2Planner built from parameter dictionaries in which nothing is at its default (horizon 7, K_s != K_g, x_lims (-3, 8), y_lims (-4, 6), sigma, epsilon,
+  radius, damping, Q_c_inv = 2.5 I; velocity limits v_x != v_y; the non-holonomic weight): step() and PlanLayer.forward reproduce the reference's rows and autograd its
+  gradients, at the bounds of test_step_matches_reference_c2mini and test_autograd_matches_reference_grads."""
+  g = golden('g11_config_constants')
+  B, n = g['th'].shape[:2]
+  H, W = g['sdf'].shape[-2:]
+  sdf = T(g['sdf']).expand(B, 1, H, W)
+  im = (sdf > 0).double()
+  for key, dof, extra in (('static', 2, {}), ('vel', 2, dict(use_vel_limits=True)), ('xyh', 3, dict(non_holonomic=True))):
+    pre = 'xyh_' if dof == 3 else ''
+    planner = _nd_planner(g, B, dof, **extra)
+    dth, hidden, err, err_ext, qc, ow, eps = planner.step(T(g[pre + 'th']), T(g[pre + 'start']), T(g[pre + 'goal']), im, sdf)
+    assert dth.shape == (B, n, 2 * dof) and qc.shape == (B, n - 1, dof, dof)
+    assert rel_err(dth.cpu().numpy(), g[key + '_dth']) < 1e-9, (key, rel_err(dth.cpu().numpy(), g[key + '_dth']))
+    assert rel_err(err.cpu().numpy(), g[key + '_err']) < 1e-11, key
+    if key == 'static': assert rel_err(err_ext.cpu().numpy(), g['static_errext']) < 1e-11
+  planner = _nd_planner(g, B)
+  leaves = {k: T(g[k]).requires_grad_(True) for k in ('th', 'start', 'goal', 'qc', 'ow', 'eps')}
+  sdfB = T(g['sdf']).repeat(B, 1, 1, 1).requires_grad_(True)
+  dth, err, err_ext = planner.plan_layer(leaves['th'], leaves['start'], leaves['goal'], im, sdfB, leaves['qc'], leaves['ow'], leaves['eps'])
+  assert rel_err(dth.detach().cpu().numpy(), g['cov_dth']) < 1e-9
+  assert rel_err(err.cpu().numpy(), g['cov_err']) < 1e-11 and rel_err(err_ext.detach().cpu().numpy(), g['cov_errext']) < 1e-11
+  names = ('th', 'start', 'goal', 'qc', 'ow', 'eps')
+  grads = torch.autograd.grad((T(g['gbar']) * dth).sum(), [leaves[k] for k in names] + [sdfB], retain_graph=True)
+  for k, gr in zip(names + ('sdf',), grads):
+    assert rel_err(gr.cpu().numpy(), g['g_' + k]) < 1e-8, (k, rel_err(gr.cpu().numpy(), g['g_' + k]))
+  grads_e = torch.autograd.grad((T(g['gext']) * err_ext).sum(), [leaves[k] for k in names] + [sdfB], allow_unused=True)
+  for k, gr in zip(names + ('sdf',), grads_e):
+    if bool(g['ge_none_' + k]): assert gr is None or float(gr.abs().max()) == 0.0, k
+    else: assert rel_err(gr.cpu().numpy(), g['ge_' + k]) < 1e-10, (k, rel_err(gr.cpu().numpy(), g['ge_' + k]))
+  # the unweighted errors at th with the epsilons the static step left behind
+  planner = _nd_planner(g, B)
+  planner.step(T(g['th']), T(g['start']), T(g['goal']), im, sdf)
+  usg, ugp, uob = planner.unweighted_errors_batch(T(g['th']), sdf)
+  for got, k in ((usg, 'unw_sg'), (ugp, 'unw_gp'), (uob, 'unw_obs')): assert rel_err(got.cpu().numpy(), g[k]) < 1e-11, k
