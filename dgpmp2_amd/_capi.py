@@ -20,6 +20,8 @@ DGP_QC_STATIC, DGP_QC_PERSTATE, DGP_QC_QFULL, DGP_QC_SCALAR = 0, 1, 2, 3
 DGP_SDF_ROWMAJOR, DGP_SDF_TILED4 = 0, 1
 DGP_GSDF_DENSE, DGP_GSDF_DENSE_F64, DGP_GSDF_SPARSE = 0, 1, 2
 DGP_ABI_VERSION = 7
+DGP_OBST_RECT, DGP_OBST_WALL = 0, 1
+DGP_OBST_MAX_BOXES, DGP_OBST_MAX_POINTS, DGP_OBST_MAX_GENERATORS = 64, 32, 4
 # columns of dgp_traj_metrics' (B, DGP_METRIC_COUNT) float64 array, in the header's order (DGP_METRIC_*)
 METRIC_NAMES = ('avg_vel', 'avg_acc', 'avg_jerk', 'gp_mse', 'in_coll', 'num_penetrating', 'avg_penetration', 'max_penetration', 'coll_intensity',
                 'constraint_violation', 'pos_mse', 'vel_mse', 'traj_mse')
@@ -52,6 +54,12 @@ class DgpSampleParams(C.Structure):
               ('corner_inset', C.c_double)]
 
 
+class DgpObstacleParams(C.Structure):
+  _fields_ = [('kind', C.c_int32), ('n_lo', C.c_int32), ('n_hi', C.c_int32), ('w_min', C.c_int32), ('w_max', C.c_int32), ('h_min', C.c_int32), ('h_max', C.c_int32),
+              ('start_x', C.c_int32), ('start_y', C.c_int32), ('end_x', C.c_int32), ('end_y', C.c_int32), ('max_draws', C.c_int32),
+              ('patch_size_obs', C.c_double), ('patch_size', C.c_double)]
+
+
 class DgpError(RuntimeError):
   def __init__(self, code, msg):
     super(DgpError, self).__init__('dgpmp2_hip error %d: %s' % (code, msg))
@@ -63,7 +71,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -121,6 +129,11 @@ class CApi(object):
     if self.sample_problems is not None:
       self.sample_problems.restype = C.c_int
       self.sample_problems.argtypes = [vp, i32, C.POINTER(DgpSdf), vp, C.POINTER(DgpSampleParams), C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
+    # dgp_obstacle_maps: no twin in the emulator either
+    self.obstacle_maps = getattr(self.lib, prefix + 'obstacle_maps', None)
+    if self.obstacle_maps is not None:
+      self.obstacle_maps.restype = C.c_int
+      self.obstacle_maps.argtypes = [vp, i32, i32, i32, C.POINTER(DgpObstacleParams), i32, C.c_uint64, C.c_uint64, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     self.time_next_launch = f('time_next_launch'); self.time_next_launch.restype = C.c_int; self.time_next_launch.argtypes = [vp, vp]
     self.event_create = f('event_create'); self.event_create.restype = C.c_int; self.event_create.argtypes = [C.POINTER(vp)]
     self.event_destroy = f('event_destroy'); self.event_destroy.restype = None; self.event_destroy.argtypes = [vp]
@@ -377,6 +390,27 @@ class Solver(object):
       raise NotImplementedError('%s does not export %ssample_problems (the CPU emulator has no twin of the sampler kernel)' % (self.api.path, self.api.prefix))
     self.api.check(self.api.sample_problems(self.handle, batch, C.byref(sdf) if sdf is not None else None, env_index, C.byref(params) if params is not None else None,
                                             int(seed), int(first_problem), diagonal, start, goal, th_init, draws, info, stream))
+
+  @staticmethod
+  def obstacle_params(kind, n_lo, n_hi, w_min, w_max, h_min, h_max, start_x=0, start_y=0, end_x=0, end_y=0, patch_size_obs=0.0, patch_size=0.0, max_draws=4096):
+    """DgpObstacleParams: one generator of dgp_obstacle_maps (a wall reads h_min / h_max as its gap widths and start_y as gap_y); max_draws bounds the reference's
+    endless loop per obstacle."""
+    return DgpObstacleParams(int(kind), int(n_lo), int(n_hi), int(w_min), int(w_max), int(h_min), int(h_max), int(start_x), int(start_y), int(end_x), int(end_y),
+                             int(max_draws), float(patch_size_obs), float(patch_size))
+
+  def obstacle_maps(self, batch, rows, cols, params, image, image_dtype=DGP_U8, seed=0, first_env=0, start_pts=None, goal_pts=None, num_pts=0, boxes=None,
+                    num_boxes=None, draws=None, info=None, stream=None):
+    """dgp_obstacle_maps: image (B,rows,cols) of image_dtype, boxes (B,64,4), num_boxes (B), draws (B,64) and info (B) int32, one launch.  params: one
+    DgpObstacleParams or a sequence of them (one is drawn per environment); start_pts / goal_pts: (B,num_pts,2) float64 device arrays or None."""
+    if self.api.obstacle_maps is None:
+      raise NotImplementedError('%s does not export %sobstacle_maps (the CPU emulator has no twin of the obstacle-map kernel)' % (self.api.path, self.api.prefix))
+    if params is None: arr, n = None, 0
+    elif isinstance(params, DgpObstacleParams): arr, n = C.pointer(params), 1
+    else:
+      n = len(params)
+      arr = (DgpObstacleParams * max(n, 1))(*params)
+    self.api.check(self.api.obstacle_maps(self.handle, int(batch), int(rows), int(cols), arr, n, int(seed), int(first_env), start_pts, goal_pts, int(num_pts), image,
+                                          int(image_dtype), boxes, num_boxes, draws, info, stream))
 
   def eval_errors_backward(self, batch, th, start, goal, sdf, covs, g_err_ext=None, g_unw_sg=None, g_unw_gp=None, g_unw_obs=None,
                            g_th=None, g_start=None, g_goal=None, g_sdf=None, g_sdf_batch_stride=0, g_eps=None, stream=None, g_sdf_copies=1):

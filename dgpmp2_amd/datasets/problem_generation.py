@@ -3,8 +3,9 @@
 Reference: datasets/generate_optimal_paths_gpmp2.py (get_random_2d_confs :54-81, generate_start_goal :120-162) and datasets/generate_2d_dataset.py (:205-265):
 images -> SDFs -> feasible start / goal pairs -> straight-line initial trajectories -> planner.forward() -> collision check -> files.  The reference finds the pairs in
 Python rejection loops, one Env2D.is_feasible call per candidate point; here every problem of a batch is sampled by ONE launch (dgp_sample_problems,
-csrc/problem_sampler.hip) with counter-based randomness: problem number p of a seed is the same problem whatever batch it is drawn in.  RRT* initialisation (OMPL),
-the obstacle-map generators and plotting are not part of this build: images are an input.
+csrc/problem_sampler.hip) with counter-based randomness: problem number p of a seed is the same problem whatever batch it is drawn in.  The images are an input, or
+made on the device as well (datasets/obstacle_maps.py, dgp_obstacle_maps: the reference's obst_generator.py): generate_dataset then starts from a seed.  RRT*
+initialisation (OMPL) and plotting are not part of this build.
 """
 import numpy as np
 import torch
@@ -68,8 +69,11 @@ def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, c
   return startb, goalb, th_initb, SampleInfo(info, draws)
 
 
-def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, first_diagonal=True, require_collision_free=True, **params):
+def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, first_diagonal=True, require_collision_free=True, dataset_type=None, num_envs=None,
+                     im_size=None, obstacle_params=None, **params):
   """The reference's generation chain for a batch of environments, on the device until the files are written:
+    0. images=None: generate_obstacle_maps(planner, dataset_type, num_envs, im_size, seed=seed, **obstacle_params) makes the images (uint8); an environment whose
+       map is flagged capped or overlapping is dropped before anything else runs           (generate_2d_dataset.py:194-208; the reference never returns such a map)
     1. sdf_2d_batch(images, padlen=0, res=cell_size)                              (generate_2d_dataset.py:211; cell_size = (x_max - x_min) / image width)
     2. sample_problems: probs_per_env problems per environment; with first_diagonal the first problem of every environment is one of the four diagonals, drawn
        from `seed`                                                                (generate_optimal_paths_gpmp2.py:126-148)
@@ -79,8 +83,31 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
   images: (E,H,W) or (E,1,H,W) device tensor, free space > 0.75.  An environment with a problem whose sampling hit max_draws is dropped; so is one with a planned
   trajectory in collision when require_collision_free is set (the reference drops an environment by exception, :247-265).  Written environments are numbered densely.
   **params go to sample_problems.  -> {'num_envs': written, 'kept': [input indices], 'dropped': {input index: reason}, 'start', 'goal', 'th_init', 'th_opt': device
-  tensors of ALL E * probs_per_env problems (problem e * probs_per_env + j), 'info': SampleInfo, 'in_coll': (E * probs_per_env,) bool}."""
+  tensors of ALL E * probs_per_env problems (problem e * probs_per_env + j), 'info': SampleInfo, 'in_coll': (E * probs_per_env,) bool}.  With images=None, 'kept' and
+  'dropped' count in the num_envs generated environments, E is the number of them that went through the chain, and 'images' (E,1,H,W), 'env_numbers' (their numbers
+  among the generated ones) and 'obstacle_info' (ObstacleInfo of all num_envs) are returned as well."""
   from ..utils.sdf_utils import sdf_2d_batch
+  if images is None:
+    from .obstacle_maps import generate_obstacle_maps
+    if dataset_type is None or num_envs is None or im_size is None: raise ValueError('generate_dataset: without images, dataset_type, num_envs and im_size say what to generate')
+    gen, oinfo = generate_obstacle_maps(planner, dataset_type, num_envs, im_size, seed=seed, **(obstacle_params or {}))
+    capped_h, over_h = oinfo.capped.cpu().numpy(), oinfo.overlapping.cpu().numpy()
+    good = [e for e in range(int(num_envs)) if not (capped_h[e] or over_h[e])]
+    sel = torch.tensor(good, dtype=torch.long, device=gen.device)
+    r = {'num_envs': 0, 'kept': [], 'dropped': {}}
+    if good:
+      r = generate_dataset(root_dir, mode, gen[sel], planner, probs_per_env, seed=seed, first_diagonal=first_diagonal,
+                           require_collision_free=require_collision_free, **params)
+    else:
+      write_meta(root_dir, mode, 0, int(probs_per_env), {'x_lims': [float(v) for v in planner.env_params['x_lims']], 'y_lims': [float(v) for v in planner.env_params['y_lims']]},
+                 int(gen.shape[-1]))
+    r['kept'] = [good[k] for k in r['kept']]
+    r['dropped'] = {good[k]: why for k, why in r['dropped'].items()}
+    for e in range(int(num_envs)):
+      if capped_h[e]: r['dropped'][e] = 'no valid obstacle within max_draws candidates'
+      elif over_h[e]: r['dropped'][e] = 'obstacles overlap'
+    r.update(images=gen[sel], env_numbers=good, obstacle_info=oinfo)
+    return r
   if not torch.is_tensor(images) or not images.is_cuda: raise RuntimeError('dgpmp2_amd.generate_dataset: `images` must be a CUDA/ROCm tensor; this build has no CPU path')
   layer = planner.plan_layer
   im = images[:, 0] if images.dim() == 4 else images

@@ -42,7 +42,7 @@ extern "C" {
 /* io_dtype */
 #define DGP_F32 0
 #define DGP_F64 1
-#define DGP_U8  2   /* dgp_sdf_2d images only */
+#define DGP_U8  2   /* images only: dgp_sdf_2d (input), dgp_obstacle_maps (output) */
 
 /* flags */
 #define DGP_FLAG_NONHOLONOMIC 1u   /* planner_params['non_holonomic'] (plan_layer.py:32), needs dof == 3 */
@@ -386,6 +386,60 @@ typedef struct DgpSampleParams {
 int dgp_sample_problems(const DgpHandle* h, int32_t batch, const DgpSdf* sdf, const int32_t* env_index,
                         const DgpSampleParams* p, uint64_t seed, uint64_t first_problem, const int32_t* diagonal,
                         void* start, void* goal, void* th_init, int32_t* draws, int32_t* info, void* stream);
+
+/* Obstacle maps generated on the device, ONE launch: the occupancy images of a batch of environments -- what the reference makes with one Python rejection loop per
+ * obstacle that copies and repaints the whole map for every candidate:
+ *   generate_rect_obstacle_map / generate_wall_obstacle_map (datasets/obst_generator.py:179-221, :226-268) over random_rect / random_wall (:130-146), the checks
+ *   _obstacle_collision_check (:45-50, :89-94) and _point_collision_check (:52-64, :96-108) and the slices of _add_to_map (:72-77, :115-126) and _add_point_to_map
+ *   (:66-69), with the parameters of get_tarpit / get_forest / get_multi_obs / get_passage (datasets/generate_2d_dataset.py:29-75).
+ * The rule is the reference's, quirks included (tests/golden/g11_obstacles.npz pins it).  Rows are axis 0 (y), columns axis 1 (x).  Obstacles are placed one after
+ * another; candidate k of an obstacle is valid iff, after adding it to a copy of the map, no cell exceeds 1 -- in the obstacle check (a rectangle grown by pad_obs on
+ * every side, a wall as it is) and, where keep-out points are given, for the obstacle without padding together with each point's patch.  A rectangle (w, h, cx, cy)
+ * paints rows [cy - ceil(h/2), cy + ceil(h/2)) x columns [cx - ceil(w/2), cx + ceil(w/2)); a wall (w, gw, cx, gy) paints rows [0, gy - ceil(gw/2)) and
+ * [gy + ceil(gw/2), rows) x columns [cx - ceil(w/2), cx + ceil(w/2)): two boxes; the patch of a point (x, y) is rows [ceil(y) - pad_pt, ceil(y) + pad_pt) x columns
+ * [ceil(x) - pad_pt, ceil(x) + pad_pt).  Every range is a NumPy slice: a negative bound has the axis length added, both bounds are then clamped to [0, N], and the
+ * slice is empty where start >= stop.  A padded box that sticks out over the low edge is therefore EMPTY and its check vacuous, as in the reference.  Once the map holds
+ * a cell above 1 (two placed boxes overlap, or a placed box lies on a patch) no candidate is valid any more.
+ * Randomness is counter-based -- Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (env lo, env hi, k, stream), env = first_env + b.  An inclusive
+ * integer range [a, b] is drawn from a word w as a + ((uint64)w * (b - a + 1) >> 32).  Stream i holds the candidates of obstacle i, k the draw index:
+ *   rectangle: w0 -> w in [w_min, w_max], w1 -> h in [h_min, h_max], w2 -> cx in [start_x + ceil(w/2), end_x - ceil(w/2)], w3 -> cy in [start_y + ceil(h/2),
+ *              end_y - ceil(h/2)]                                                                                                    (random_rect, :130-139)
+ *   wall:      w0 -> w in [w_min, w_max], w1 -> gw in [h_min, h_max], w2 -> cx in [start_x + ceil(w/2), cols - ceil(w/2)], w3 -> gy in [start_y + ceil(gw/2),
+ *              rows - ceil(gw/2)]   (random_wall, :141-146, start_y its gap_y; the reference bounds both by the side of its square maps)
+ * and the accepted candidate is the lowest valid k.  Stream 0xffffffff, k = 0: w0 gives the obstacle count n_lo + ((uint64)w0 * (n_hi - n_lo) >> 32) of the half-open
+ * range [n_lo, n_hi) (np.random.randint(5, 8)), w1 the generator ((uint64)w1 * num_params >> 32) of the environment where several are passed (mixed_clutter).  An
+ * environment is a pure function of (seed, first_env + b), the parameters and its keep-out points: independent of batch size, position in the batch and launch shape.
+ * Each obstacle's loop stops after max_draws candidates (the reference loops for ever): the last candidate, k = max_draws - 1, is then placed.
+ * params: num_params (1 .. DGP_OBST_MAX_GENERATORS) generators.  start_pts / goal_pts: (batch, num_pts, 2) float64 device arrays of pixel coordinates (x, y) as
+ * generate_2d_dataset.py:186-192 forms them, or NULL; num_pts <= DGP_OBST_MAX_POINTS per list.
+ * Outputs: image (batch, rows, cols) of image_dtype DGP_U8 / DGP_F32 / DGP_F64, the reference's 1 - count (floating types; below 0 where boxes overlap) or 1 where free
+ *   and 0 otherwise (DGP_U8, what dgp_sdf_2d takes); boxes (batch, DGP_OBST_MAX_BOXES, 4) int32 [r0, r1, c0, c1], the slices as painted (clamped; empty where
+ *   r0 >= r1 or c0 >= c1), zeros past num_boxes; num_boxes (batch) int32; draws (batch, DGP_OBST_MAX_BOXES) int32, the accepted k of every obstacle, -1 past the last;
+ *   info (batch) int32: bit 0 an obstacle's loop hit max_draws, bit 1 a cell of the finished map is covered more than once (the reference's outer `while True`
+ *   never returns then), bit 2 a negative slice bound was met by a keep-out patch or by the painted or padded box of an accepted candidate.  All but image may be NULL.
+ * DGP_EINVAL, nothing launched: a NULL handle, image or params; batch < 1; num_params or num_pts out of range; an obstacle count range that is empty or allows more
+ * than DGP_OBST_MAX_BOXES boxes (a wall is two); max_draws < 1; a size range that is empty, negative or leaves no centre for its largest obstacle (the reference's
+ * randint raises there); NaN paddings; sides or coordinates beyond 2^20.
+ * One launch, no atomics, nothing allocated or synchronised: capturable in a HIP graph. */
+#define DGP_OBST_RECT            0
+#define DGP_OBST_WALL            1
+#define DGP_OBST_MAX_BOXES      64
+#define DGP_OBST_MAX_POINTS     32
+#define DGP_OBST_MAX_GENERATORS  4
+typedef struct DgpObstacleParams {
+  int32_t  kind;             /* DGP_OBST_RECT / DGP_OBST_WALL */
+  int32_t  n_lo, n_hi;       /* obstacle count in [n_lo, n_hi) */
+  int32_t  w_min, w_max;     /* widths (columns) */
+  int32_t  h_min, h_max;     /* rectangle: heights (rows); wall: gap widths gw_min, gw_max */
+  int32_t  start_x, start_y; /* lower ends of the centre ranges; wall: start_y is gap_y */
+  int32_t  end_x, end_y;     /* rectangle: upper ends of the centre ranges; wall: not read (cols, rows) */
+  int32_t  max_draws;        /* bound on the candidates of one obstacle; the reference loops for ever */
+  double   patch_size_obs;   /* rectangle: pad_obs = ceil(patch_size_obs / 2) cells between obstacles (:75-76); wall: no padding (not a NaN all the same) */
+  double   patch_size;       /* pad_pt = ceil(patch_size / 2): half side of a keep-out patch (:67-68) */
+} DgpObstacleParams;
+int dgp_obstacle_maps(const DgpHandle* h, int32_t batch, int32_t rows, int32_t cols, const DgpObstacleParams* params, int32_t num_params, uint64_t seed,
+                      uint64_t first_env, const double* start_pts, const double* goal_pts, int32_t num_pts, void* image, int32_t image_dtype,
+                      int32_t* boxes, int32_t* num_boxes, int32_t* draws, int32_t* info, void* stream);
 
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
