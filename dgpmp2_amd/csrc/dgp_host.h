@@ -4,14 +4,13 @@
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>
-#include <stdarg.h>
 #include <string.h>
 #include <math.h>
 #include <new>
 #include "gn_lane.h"
 #include "gn_backward.h"
 #include "gn_long.h"
-#include "../../include/dgpmp2_hip.h"
+#include "dgp_status.h"      // err_buf, fail, LaunchEvents, launch_events (and include/dgpmp2_hip.h)
 
 struct DgpHandle {
   DgpConfig cfg;
@@ -25,27 +24,6 @@ struct DgpHandle {
 struct DgpShape { int lpt, c; };
 
 namespace dgp_host {
-
-inline char* err_buf() {
-  static thread_local char buf[512] = "";
-  return buf;
-}
-
-// dgp_time_next_launch: the event pair the calling thread's next launch records its begin / end on (one variable per thread
-// across all translation units of the library)
-struct LaunchEvents { void* start; void* stop; };
-inline LaunchEvents& launch_events() {
-  static thread_local LaunchEvents ev = {nullptr, nullptr};
-  return ev;
-}
-
-inline int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(err_buf(), 512, fmt, ap);
-  va_end(ap);
-  return code;
-}
 
 // Shapes the kernels are instantiated for (with_kernel_args below): LPT in {16,32,64} x C in {1,2,4}.
 constexpr int kMaxStates = 256;
@@ -110,10 +88,6 @@ enum { MODE_STEP = dgp::MODE_STEP, MODE_SOLVE = dgp::MODE_SOLVE, MODE_EVAL = dgp
 constexpr int shape_family(int mode, int qk) {
   return mode == MODE_EVAL ? FAM_STATIC : (qk == dgp::QK_GENERAL ? FAM_GENERAL : ((qk == dgp::QK_KRON && mode == MODE_BACKWARD) ? FAM_KRON_BWD : FAM_STATIC));
 }
-// The two names tests/emul/emul_main.cpp took from this header before choose_kernel, kept so that the emulator source of the commit before this one still
-// compiles against this header (that commit's tests then run against this library).  Nothing in the tree uses them.
-enum { kModeStepErrs = MODE_STEP_ERRS };
-inline int shape_family(int mode, const dgp::GnParams& p) { return shape_family(mode, dgp::kernel_variant(p)); }
 // Unit family: the three builds of gn_inst.hip (dgpmp2_amd/_build/units.py) -- the standard kernels, their twins for 4 x 4-tiled grids (-DDGP_TL=1) and the step
 // kernels with the errors epilogue (-DDGP_STEP_ERRS=1); the values are those of the kernels' trailing template argument, DGP_TL + 2 * DGP_STEP_ERRS.
 enum { UNIT_STANDARD = 0, UNIT_TILED = 1, UNIT_STEP_ERRS = 2, NUM_UNITS = 3, UNIT_ANY = NUM_UNITS };
@@ -528,8 +502,27 @@ inline int fill_solve_backward(const DgpHandle* h, int32_t batch, const void* st
   return DGP_OK;
 }
 
-// ---- the round-4 entry points, generic over how a kernel is launched (HIP: dgpmp2_hip.hip; the test emulator: tests/emul) ------------------
+// ---- the entry points that launch the solver's kernels, generic over how a kernel is launched (HIP: dgpmp2_hip.hip; the test emulator: tests/emul) ------------------
 // `launch(mode, p, g)` -> DGP_OK or an error code; mode: MODE_* above.
+
+template <typename Launch>
+int eval_errors(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf, const DgpCovs* covs, void* err,
+                void* err_ext, void* unw_sg, void* unw_gp, void* unw_obs, Launch&& launch) {
+  dgp::GnParams p;
+  const int rc = fill_eval(h, batch, th, start, goal, sdf, covs, err, err_ext, unw_sg, unw_gp, unw_obs, p);
+  return rc != DGP_OK ? rc : launch((int)MODE_EVAL, p, (const dgp::GnGradParams*)nullptr);
+}
+
+template <typename Launch>
+int eval_errors_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf, const DgpCovs* covs,
+                         const void* g_err_ext, const void* g_unw_sg, const void* g_unw_gp, const void* g_unw_obs, void* g_th, void* g_start, void* g_goal,
+                         void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies, void* g_eps, Launch&& launch) {
+  dgp::GnParams p;
+  dgp::GnGradParams g;
+  const int rc = fill_eval_backward(h, batch, th, start, goal, sdf, covs, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start, g_goal, g_sdf,
+                                    g_sdf_batch_stride, g_sdf_copies, g_eps, p, g);
+  return rc != DGP_OK ? rc : launch((int)MODE_BACKWARD, p, &g);
+}
 
 template <typename Launch>
 int gn_solve_traced(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf, const DgpCovs* covs,
@@ -622,6 +615,27 @@ int gn_step_errors_backward(const DgpHandle* h, int32_t batch, const void* th, c
     p.vec_io = (p.vec_io && aligned16(workspace)) ? 1 : 0;
   }
   return launch((int)MODE_BACKWARD, p, &g);
+}
+
+// dgp_gn_solve, dgp_gn_step and dgp_gn_step_backward are the calls above without their extensions: no history, no unweighted errors, no error cotangents
+// (the same checks in the same order, one launch)
+template <typename Launch>
+int gn_solve(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf, const DgpCovs* covs,
+             int32_t max_iters, double tol_delta, void* th_out, int32_t* iters, void* err_hist, void* errext_hist, void* err_final, int32_t* info,
+             Launch&& launch) {
+  return gn_solve_traced(h, batch, th_init, start, goal, sdf, covs, max_iters, tol_delta, th_out, iters, err_hist, errext_hist, err_final, info, nullptr, launch);
+}
+template <typename Launch>
+int gn_step(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf, const DgpCovs* covs, void* dtheta,
+            void* err, void* err_ext, int32_t* info, Launch&& launch) {
+  return gn_step_errors(h, batch, th, start, goal, sdf, covs, dtheta, err, err_ext, info, nullptr, nullptr, nullptr, launch);
+}
+template <typename Launch>
+int gn_step_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf, const DgpCovs* covs,
+                     const void* dtheta, const void* g_dtheta, const void* g_err_ext, void* g_th, void* g_start, void* g_goal, void* g_sdf,
+                     int64_t g_sdf_batch_stride, int32_t g_sdf_copies, void* g_qc_inv, void* g_obs_w, void* g_eps, Launch&& launch) {
+  return gn_step_errors_backward(h, batch, th, start, goal, sdf, covs, dtheta, g_dtheta, g_err_ext, nullptr, nullptr, nullptr, g_th, g_start, g_goal, g_sdf,
+                                 g_sdf_batch_stride, g_sdf_copies, g_qc_inv, g_obs_w, g_eps, nullptr, launch);
 }
 
 }  // namespace dgp_host

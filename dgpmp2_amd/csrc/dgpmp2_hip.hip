@@ -8,44 +8,49 @@
 namespace {
 
 using dgp_host::fail;
+using dgp_dev::hip_rc;
 
-// a call that fails validation launches nothing: a pending dgp_time_next_launch request must not attach to an unrelated later launch
-int drop_events(int rc) {
-  dgp_host::LaunchEvents& le = dgp_host::launch_events();
-  le.start = le.stop = nullptr;
-  return rc;
-}
+// How the entry points below launch (dgp_host.h: their host logic is shared with the test emulator).  Made when an entry point is entered, which is when the calling
+// thread's dgp_time_next_launch request is taken (dgp_launch.h): a call that fails validation has used it up and launched nothing, the first launch gets it.
+struct HipLaunch {
+  const DgpHandle* h; hipStream_t s; const char* what;
+  dgp_dev::Events ev = dgp_dev::take_events();
+  // One launch: dgp_host::choose_kernel says which kernel, the table which translation unit holds it.
+  int operator()(int mode, const dgp::GnParams& p, const dgp::GnGradParams* g) {
+    dgp_host::KernelChoice kc;
+    const int rc = dgp_host::choose_kernel(h, mode, p, what, kc);
+    if (rc != DGP_OK) return rc;
+    const int f64 = h->cfg.io_dtype == DGP_F64 ? 1 : 0;
+    if (kc.is_long) {      // n > 256: gn_long.h
+      dgp_dev::pass_events(ev);
+      return hip_rc(dgp_launch_long(h->cfg.dof, f64 != 0, kc.mode, p, g, s), what);
+    }
+    // [unit family][dof - 2][io dtype][kernel group] -> the launcher of the translation unit that holds the kernel (gn_inst.hip; dgpmp2_amd/_build/units.py builds exactly
+    // these); null: not built -- the step-errors twins have no backward kernels, and no general ones for d = 6
+    static DgpLaunch* const table[dgp_host::NUM_UNITS][2][2][dgp_host::NUM_GROUPS] = {
+        {{{dgp_launch_2_f32_g0, dgp_launch_2_f32_g1, dgp_launch_2_f32_g2, dgp_launch_2_f32_g3, dgp_launch_2_f32_g4},
+          {dgp_launch_2_f64_g0, dgp_launch_2_f64_g1, dgp_launch_2_f64_g2, dgp_launch_2_f64_g3, dgp_launch_2_f64_g4}},
+         {{dgp_launch_3_f32_g0, dgp_launch_3_f32_g1, dgp_launch_3_f32_g2, dgp_launch_3_f32_g3, dgp_launch_3_f32_g4},
+          {dgp_launch_3_f64_g0, dgp_launch_3_f64_g1, dgp_launch_3_f64_g2, dgp_launch_3_f64_g3, dgp_launch_3_f64_g4}}},
+        {{{dgp_launch_2t_f32_g0, dgp_launch_2t_f32_g1, dgp_launch_2t_f32_g2, dgp_launch_2t_f32_g3, dgp_launch_2t_f32_g4},
+          {dgp_launch_2t_f64_g0, dgp_launch_2t_f64_g1, dgp_launch_2t_f64_g2, dgp_launch_2t_f64_g3, dgp_launch_2t_f64_g4}},
+         {{dgp_launch_3t_f32_g0, dgp_launch_3t_f32_g1, dgp_launch_3t_f32_g2, dgp_launch_3t_f32_g3, dgp_launch_3t_f32_g4},
+          {dgp_launch_3t_f64_g0, dgp_launch_3t_f64_g1, dgp_launch_3t_f64_g2, dgp_launch_3t_f64_g3, dgp_launch_3t_f64_g4}}},
+        {{{dgp_launch_2e_f32_g0, dgp_launch_2e_f32_g1, nullptr, dgp_launch_2e_f32_g3, nullptr},
+          {dgp_launch_2e_f64_g0, dgp_launch_2e_f64_g1, nullptr, dgp_launch_2e_f64_g3, nullptr}},
+         {{dgp_launch_3e_f32_g0, nullptr, nullptr, dgp_launch_3e_f32_g3, nullptr},
+          {dgp_launch_3e_f64_g0, nullptr, nullptr, dgp_launch_3e_f64_g3, nullptr}}}};
+    DgpLaunch* const unit = table[kc.unit][h->cfg.dof - 2][f64][kc.group];
+    if (!unit) return fail(DGP_EUNSUPPORTED, "%s: the kernel of this launch is not built (unit family %d, group %d)", what, kc.unit, kc.group);
+    dgp_dev::pass_events(ev);
+    return hip_rc(unit(kc, p, g, s), what);
+  }
+};
 
-int hip_rc(hipError_t e, const char* what) {
-  if (e == hipSuccess) return DGP_OK;
-  return fail(DGP_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
-}
-
-// One launch of entry point `what`: dgp_host::choose_kernel says which kernel, the table which translation unit holds it.
-int launch(const DgpHandle* h, int mode, const dgp::GnParams& p, const dgp::GnGradParams* g, hipStream_t s, const char* what) {
-  dgp_host::KernelChoice kc;
-  const int rc = dgp_host::choose_kernel(h, mode, p, what, kc);
-  if (rc != DGP_OK) return drop_events(rc);
-  const int f64 = h->cfg.io_dtype == DGP_F64 ? 1 : 0;
-  if (kc.is_long) return hip_rc(dgp_launch_long(h->cfg.dof, f64 != 0, kc.mode, p, g, s), what);      // n > 256: gn_long.h
-  // [unit family][dof - 2][io dtype][kernel group] -> the launcher of the translation unit that holds the kernel (gn_inst.hip; dgpmp2_amd/_build/units.py builds exactly
-  // these); null: not built -- the step-errors twins have no backward kernels, and no general ones for d = 6
-  static DgpLaunch* const table[dgp_host::NUM_UNITS][2][2][dgp_host::NUM_GROUPS] = {
-      {{{dgp_launch_2_f32_g0, dgp_launch_2_f32_g1, dgp_launch_2_f32_g2, dgp_launch_2_f32_g3, dgp_launch_2_f32_g4},
-        {dgp_launch_2_f64_g0, dgp_launch_2_f64_g1, dgp_launch_2_f64_g2, dgp_launch_2_f64_g3, dgp_launch_2_f64_g4}},
-       {{dgp_launch_3_f32_g0, dgp_launch_3_f32_g1, dgp_launch_3_f32_g2, dgp_launch_3_f32_g3, dgp_launch_3_f32_g4},
-        {dgp_launch_3_f64_g0, dgp_launch_3_f64_g1, dgp_launch_3_f64_g2, dgp_launch_3_f64_g3, dgp_launch_3_f64_g4}}},
-      {{{dgp_launch_2t_f32_g0, dgp_launch_2t_f32_g1, dgp_launch_2t_f32_g2, dgp_launch_2t_f32_g3, dgp_launch_2t_f32_g4},
-        {dgp_launch_2t_f64_g0, dgp_launch_2t_f64_g1, dgp_launch_2t_f64_g2, dgp_launch_2t_f64_g3, dgp_launch_2t_f64_g4}},
-       {{dgp_launch_3t_f32_g0, dgp_launch_3t_f32_g1, dgp_launch_3t_f32_g2, dgp_launch_3t_f32_g3, dgp_launch_3t_f32_g4},
-        {dgp_launch_3t_f64_g0, dgp_launch_3t_f64_g1, dgp_launch_3t_f64_g2, dgp_launch_3t_f64_g3, dgp_launch_3t_f64_g4}}},
-      {{{dgp_launch_2e_f32_g0, dgp_launch_2e_f32_g1, nullptr, dgp_launch_2e_f32_g3, nullptr},
-        {dgp_launch_2e_f64_g0, dgp_launch_2e_f64_g1, nullptr, dgp_launch_2e_f64_g3, nullptr}},
-       {{dgp_launch_3e_f32_g0, nullptr, nullptr, dgp_launch_3e_f32_g3, nullptr},
-        {dgp_launch_3e_f64_g0, nullptr, nullptr, dgp_launch_3e_f64_g3, nullptr}}}};
-  DgpLaunch* const unit = table[kc.unit][h->cfg.dof - 2][f64][kc.group];
-  if (!unit) return drop_events(fail(DGP_EUNSUPPORTED, "%s: the kernel of this launch is not built (unit family %d, group %d)", what, kc.unit, kc.group));
-  return hip_rc(unit(kc, p, g, s), what);
+// the element-wise kernels below: 256 lanes per block, one element per lane and trip, at most 4096 blocks
+dim3 grid256(int64_t elems) {
+  const int64_t blocks = (elems + 255) / 256;
+  return dim3((unsigned)(blocks > 4096 ? 4096 : blocks));
 }
 
 // dgp_sum_partial_grids: out[e] = scale * sum_c partial[c][e] -- the partial copies of a shared grid's gradient (dgp_gn_step_backward's g_sdf_copies) summed and cast in
@@ -127,15 +132,13 @@ int dgp_square_covariances(const void* raw, int32_t dtype, int32_t batch, int32_
                            void* sq_scalars, void* sq_qc_inv, void* sq_obs_w, void* sq_eps, void* stream) {
   int rc = square_covs_check(raw, dtype, batch, width, n_gp, num_states, learn_eps, dof);
   if (rc != DGP_OK) return rc;
-  const int64_t total = (int64_t)batch * width, blocks64 = (total + 255) / 256;
-  const dim3 grid((unsigned)(blocks64 > 4096 ? 4096 : blocks64)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == DGP_F64) hipLaunchKernelGGL((square_covs_kernel<double>), grid, block, 0, s, (const double*)raw, batch, width, n_gp, num_states, learn_eps, dof, (double*)sq_scalars,
-                                           (double*)sq_qc_inv, (double*)sq_obs_w, (double*)sq_eps);
-  else hipLaunchKernelGGL((square_covs_kernel<float>), grid, block, 0, s, (const float*)raw, batch, width, n_gp, num_states, learn_eps, dof, (float*)sq_scalars, (float*)sq_qc_inv,
-                          (float*)sq_obs_w, (float*)sq_eps);
-  const hipError_t e = hipGetLastError();
-  return hip_rc(e, "dgp_square_covariances");
+  auto run = [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((square_covs_kernel<T>), grid256((int64_t)batch * width), dim3(256), 0, (hipStream_t)stream, (const T*)raw, batch, width, n_gp, num_states, learn_eps, dof,
+                       (T*)sq_scalars, (T*)sq_qc_inv, (T*)sq_obs_w, (T*)sq_eps);
+  };
+  if (dtype == DGP_F64) run(double()); else run(float());
+  return hip_rc(hipGetLastError(), "dgp_square_covariances");
 }
 
 int dgp_square_covariances_backward(const void* raw, int32_t dtype, int32_t batch, int32_t width, int32_t n_gp, int32_t num_states, int32_t learn_eps, int32_t dof,
@@ -143,33 +146,27 @@ int dgp_square_covariances_backward(const void* raw, int32_t dtype, int32_t batc
   int rc = square_covs_check(raw, dtype, batch, width, n_gp, num_states, learn_eps, dof);
   if (rc != DGP_OK) return rc;
   if (!g_raw) return fail(DGP_EINVAL, "dgp_square_covariances_backward: null g_raw");
-  const int64_t total = (int64_t)batch * width, blocks64 = (total + 255) / 256;
-  const dim3 grid((unsigned)(blocks64 > 4096 ? 4096 : blocks64)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == DGP_F64) hipLaunchKernelGGL((square_covs_backward_kernel<double>), grid, block, 0, s, (const double*)raw, batch, width, n_gp, num_states, learn_eps, dof,
-                                           (const double*)g_qc_inv, (const double*)g_obs_w, (const double*)g_eps, (double*)g_raw);
-  else hipLaunchKernelGGL((square_covs_backward_kernel<float>), grid, block, 0, s, (const float*)raw, batch, width, n_gp, num_states, learn_eps, dof, (const float*)g_qc_inv,
-                          (const float*)g_obs_w, (const float*)g_eps, (float*)g_raw);
-  const hipError_t e = hipGetLastError();
-  return hip_rc(e, "dgp_square_covariances_backward");
+  auto run = [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((square_covs_backward_kernel<T>), grid256((int64_t)batch * width), dim3(256), 0, (hipStream_t)stream, (const T*)raw, batch, width, n_gp, num_states, learn_eps,
+                       dof, (const T*)g_qc_inv, (const T*)g_obs_w, (const T*)g_eps, (T*)g_raw);
+  };
+  if (dtype == DGP_F64) run(double()); else run(float());
+  return hip_rc(hipGetLastError(), "dgp_square_covariances_backward");
 }
 
 int dgp_sum_partial_grids(const void* partial, int32_t partial_dtype, int32_t copies, int64_t elems, double scale, void* out, int32_t out_dtype, void* stream) {
   if (!partial || !out) return fail(DGP_EINVAL, "dgp_sum_partial_grids: null partial or out");
   if (copies < 1 || copies > 64 || elems < 1) return fail(DGP_EINVAL, "dgp_sum_partial_grids: copies must be in 1..64 and elems positive");
   if ((partial_dtype != DGP_F32 && partial_dtype != DGP_F64) || (out_dtype != DGP_F32 && out_dtype != DGP_F64)) return fail(DGP_EINVAL, "dgp_sum_partial_grids: dtypes must be DGP_F32 / DGP_F64");
-  const int64_t blocks64 = (elems + 255) / 256;
-  const dim3 grid((unsigned)(blocks64 > 4096 ? 4096 : blocks64)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (partial_dtype == DGP_F64) {
-    if (out_dtype == DGP_F64) hipLaunchKernelGGL((sum_partial_grids_kernel<double, double>), grid, block, 0, s, (const double*)partial, copies, elems, scale, (double*)out);
-    else hipLaunchKernelGGL((sum_partial_grids_kernel<double, float>), grid, block, 0, s, (const double*)partial, copies, elems, scale, (float*)out);
-  } else {
-    if (out_dtype == DGP_F64) hipLaunchKernelGGL((sum_partial_grids_kernel<float, double>), grid, block, 0, s, (const float*)partial, copies, elems, scale, (double*)out);
-    else hipLaunchKernelGGL((sum_partial_grids_kernel<float, float>), grid, block, 0, s, (const float*)partial, copies, elems, scale, (float*)out);
-  }
-  const hipError_t e = hipGetLastError();
-  return hip_rc(e, "dgp_sum_partial_grids");
+  auto run = [&](auto ti, auto to) {
+    typedef decltype(ti) TI;
+    typedef decltype(to) TO;
+    hipLaunchKernelGGL((sum_partial_grids_kernel<TI, TO>), grid256(elems), dim3(256), 0, (hipStream_t)stream, (const TI*)partial, copies, elems, scale, (TO*)out);
+  };
+  if (partial_dtype == DGP_F64) { if (out_dtype == DGP_F64) run(double(), double()); else run(double(), float()); }
+  else { if (out_dtype == DGP_F64) run(float(), double()); else run(float(), float()); }
+  return hip_rc(hipGetLastError(), "dgp_sum_partial_grids");
 }
 
 int dgp_abi_version(void) { return DGP_ABI_VERSION; }
@@ -188,86 +185,59 @@ int dgp_time_next_launch(void* start_event, void* stop_event) {
 int dgp_launch_shape(const DgpHandle* h, int32_t batch, int32_t* lpt, int32_t* c) { return dgp_host::launch_shape(h, batch, lpt, c); }
 int dgp_step_kernel_variant(const DgpHandle* h, int32_t batch) { return dgp_host::step_kernel_variant(h, batch); }
 
+// The entry points that launch the solver's kernels: validation, argument marshalling and the launches behind one call are dgp_host.h's
 int dgp_gn_step(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
                 const DgpCovs* covs, void* dtheta, void* err, void* err_ext, int32_t* info, void* stream) {
-  dgp::GnParams p;
-  int rc = dgp_host::fill_step(h, batch, th, start, goal, sdf, covs, dtheta, err, err_ext, info, p);
-  if (rc != DGP_OK) return drop_events(rc);
-  return launch(h, dgp_host::MODE_STEP, p, nullptr, (hipStream_t)stream, "dgp_gn_step");
+  return dgp_host::gn_step(h, batch, th, start, goal, sdf, covs, dtheta, err, err_ext, info, HipLaunch{h, (hipStream_t)stream, "dgp_gn_step"});
 }
 
 int dgp_gn_solve(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf,
                  const DgpCovs* covs, int32_t max_iters, double tol_delta, void* th_out, int32_t* iters, void* err_hist,
                  void* errext_hist, void* err_final, int32_t* info, void* stream) {
-  dgp::GnParams p;
-  int rc = dgp_host::fill_solve(h, batch, th_init, start, goal, sdf, covs, max_iters, tol_delta, th_out, iters, err_hist,
-                                errext_hist, err_final, info, p);
-  if (rc != DGP_OK) return drop_events(rc);
-  return launch(h, dgp_host::MODE_SOLVE, p, nullptr, (hipStream_t)stream, "dgp_gn_solve");
+  return dgp_host::gn_solve(h, batch, th_init, start, goal, sdf, covs, max_iters, tol_delta, th_out, iters, err_hist, errext_hist, err_final, info,
+                            HipLaunch{h, (hipStream_t)stream, "dgp_gn_solve"});
 }
 
 int dgp_eval_errors(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
                     const DgpCovs* covs, void* err, void* err_ext, void* unw_sg, void* unw_gp, void* unw_obs, void* stream) {
-  dgp::GnParams p;
-  int rc = dgp_host::fill_eval(h, batch, th, start, goal, sdf, covs, err, err_ext, unw_sg, unw_gp, unw_obs, p);
-  if (rc != DGP_OK) return drop_events(rc);
-  return launch(h, dgp_host::MODE_EVAL, p, nullptr, (hipStream_t)stream, "dgp_eval_errors");
+  return dgp_host::eval_errors(h, batch, th, start, goal, sdf, covs, err, err_ext, unw_sg, unw_gp, unw_obs, HipLaunch{h, (hipStream_t)stream, "dgp_eval_errors"});
 }
 
 int dgp_gn_step_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
                          const DgpCovs* covs, const void* dtheta, const void* g_dtheta, const void* g_err_ext, void* g_th,
                          void* g_start, void* g_goal, void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies, void* g_qc_inv,
                          void* g_obs_w, void* g_eps, void* stream) {
-  dgp::GnParams p;
-  dgp::GnGradParams g;
-  int rc = dgp_host::fill_backward(h, batch, th, start, goal, sdf, covs, dtheta, g_dtheta, g_err_ext, g_th, g_start, g_goal, g_sdf,
-                                   g_sdf_batch_stride, g_sdf_copies, g_qc_inv, g_obs_w, g_eps, p, g);
-  if (rc != DGP_OK) return drop_events(rc);
-  return launch(h, dgp_host::MODE_BACKWARD, p, &g, (hipStream_t)stream, "dgp_gn_step_backward");
+  return dgp_host::gn_step_backward(h, batch, th, start, goal, sdf, covs, dtheta, g_dtheta, g_err_ext, g_th, g_start, g_goal, g_sdf, g_sdf_batch_stride,
+                                    g_sdf_copies, g_qc_inv, g_obs_w, g_eps, HipLaunch{h, (hipStream_t)stream, "dgp_gn_step_backward"});
 }
 
 int dgp_eval_errors_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
                              const DgpCovs* covs, const void* g_err_ext, const void* g_unw_sg, const void* g_unw_gp, const void* g_unw_obs,
                              void* g_th, void* g_start, void* g_goal, void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies,
                              void* g_eps, void* stream) {
-  dgp::GnParams p;
-  dgp::GnGradParams g;
-  int rc = dgp_host::fill_eval_backward(h, batch, th, start, goal, sdf, covs, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start, g_goal,
-                                        g_sdf, g_sdf_batch_stride, g_sdf_copies, g_eps, p, g);
-  if (rc != DGP_OK) return drop_events(rc);
-  return launch(h, dgp_host::MODE_BACKWARD, p, &g, (hipStream_t)stream, "dgp_eval_errors_backward");
+  return dgp_host::eval_errors_backward(h, batch, th, start, goal, sdf, covs, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start, g_goal, g_sdf,
+                                        g_sdf_batch_stride, g_sdf_copies, g_eps, HipLaunch{h, (hipStream_t)stream, "dgp_eval_errors_backward"});
 }
-
-// The round-4 entry points: their host logic (validation, the two launches behind one call) is shared with the test emulator, dgp_host.h
-namespace {
-struct HipLaunch {
-  const DgpHandle* h; hipStream_t s; const char* what;
-  int operator()(int mode, const dgp::GnParams& p, const dgp::GnGradParams* g) const { return launch(h, mode, p, g, s, what); }
-};
-}  // namespace
 
 int dgp_gn_solve_traced(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf,
                         const DgpCovs* covs, int32_t max_iters, double tol_delta, void* th_out, int32_t* iters, void* err_hist,
                         void* errext_hist, void* err_final, int32_t* info, double* th_hist, void* stream) {
-  int rc = dgp_host::gn_solve_traced(h, batch, th_init, start, goal, sdf, covs, max_iters, tol_delta, th_out, iters, err_hist, errext_hist, err_final, info,
-                                     th_hist, HipLaunch{h, (hipStream_t)stream, "dgp_gn_solve_traced"});
-  return rc == DGP_OK ? rc : drop_events(rc);
+  return dgp_host::gn_solve_traced(h, batch, th_init, start, goal, sdf, covs, max_iters, tol_delta, th_out, iters, err_hist, errext_hist, err_final, info,
+                                   th_hist, HipLaunch{h, (hipStream_t)stream, "dgp_gn_solve_traced"});
 }
 
 int dgp_gn_solve_backward(const DgpHandle* h, int32_t batch, const void* start, const void* goal, const DgpSdf* sdf, int32_t max_iters,
                           const double* th_hist, const void* th_out, const int32_t* iters, const void* g_th_out, void* g_th_init, void* g_start,
                           void* g_goal, void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies, void* stream) {
-  int rc = dgp_host::gn_solve_backward(h, batch, start, goal, sdf, max_iters, th_hist, th_out, iters, g_th_out, g_th_init, g_start, g_goal, g_sdf,
-                                       g_sdf_batch_stride, g_sdf_copies, HipLaunch{h, (hipStream_t)stream, "dgp_gn_solve_backward"});
-  return rc == DGP_OK ? rc : drop_events(rc);
+  return dgp_host::gn_solve_backward(h, batch, start, goal, sdf, max_iters, th_hist, th_out, iters, g_th_out, g_th_init, g_start, g_goal, g_sdf,
+                                     g_sdf_batch_stride, g_sdf_copies, HipLaunch{h, (hipStream_t)stream, "dgp_gn_solve_backward"});
 }
 
 int dgp_gn_step_errors(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
                        const DgpCovs* covs, void* dtheta, void* err, void* err_ext, int32_t* info, void* unw_sg, void* unw_gp, void* unw_obs,
                        void* stream) {
-  int rc = dgp_host::gn_step_errors(h, batch, th, start, goal, sdf, covs, dtheta, err, err_ext, info, unw_sg, unw_gp, unw_obs,
-                                    HipLaunch{h, (hipStream_t)stream, "dgp_gn_step_errors"});
-  return rc == DGP_OK ? rc : drop_events(rc);
+  return dgp_host::gn_step_errors(h, batch, th, start, goal, sdf, covs, dtheta, err, err_ext, info, unw_sg, unw_gp, unw_obs,
+                                  HipLaunch{h, (hipStream_t)stream, "dgp_gn_step_errors"});
 }
 
 int dgp_gn_step_errors_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
@@ -275,10 +245,9 @@ int dgp_gn_step_errors_backward(const DgpHandle* h, int32_t batch, const void* t
                                 const void* g_unw_gp, const void* g_unw_obs, void* g_th, void* g_start, void* g_goal, void* g_sdf,
                                 int64_t g_sdf_batch_stride, int32_t g_sdf_copies, void* g_qc_inv, void* g_obs_w, void* g_eps, void* workspace,
                                 void* stream) {
-  int rc = dgp_host::gn_step_errors_backward(h, batch, th, start, goal, sdf, covs, dtheta, g_dtheta, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start,
-                                             g_goal, g_sdf, g_sdf_batch_stride, g_sdf_copies, g_qc_inv, g_obs_w, g_eps, workspace,
-                                             HipLaunch{h, (hipStream_t)stream, "dgp_gn_step_errors_backward"});
-  return rc == DGP_OK ? rc : drop_events(rc);
+  return dgp_host::gn_step_errors_backward(h, batch, th, start, goal, sdf, covs, dtheta, g_dtheta, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start,
+                                           g_goal, g_sdf, g_sdf_batch_stride, g_sdf_copies, g_qc_inv, g_obs_w, g_eps, workspace,
+                                           HipLaunch{h, (hipStream_t)stream, "dgp_gn_step_errors_backward"});
 }
 
 // Event helpers for dgp_time_next_launch: created / read through the HIP runtime THIS library is linked against (an event made by

@@ -1,12 +1,12 @@
 // gn_device.h -- device lane context and kernel entry points (HIP only).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #ifndef DGP_HD
 #define DGP_HD __host__ __device__ __forceinline__
 #endif
 #include "dgp_host.h"
 #include "gn_long.h"
+#include "dgp_launch.h"
 
 namespace dgp_dev {
 
@@ -229,25 +229,17 @@ __global__ void __launch_bounds__(64) gn_long_backward_kernel(const dgp::GnParam
 //  template -- the linker would keep either, and both launchers would then start the same kernels)
 template <int DOF, typename IO, int GROUP, int TL = DGP_TL + 2 * DGP_STEP_ERRS>
 hipError_t launch_typed(const dgp_host::KernelChoice& kc, const dgp::GnParams& p, const dgp::GnGradParams* g, hipStream_t s) {
+  const Events ev = take_events();      // (handed over by HipLaunch in dgpmp2_hip.hip: dgp_launch.h, pass_events)
   if (kc.unit != TL || kc.group != GROUP) return hipErrorInvalidValue;
   const int tpw = 64 / kc.sh.lpt;
   const dim3 grid((unsigned)((p.B + tpw - 1) / tpw)), block(64);
-  // dgp_time_next_launch(): this launch records its own begin / end on the caller's events (hipExtLaunchKernelGGL); one-shot
-  dgp_host::LaunchEvents& le = dgp_host::launch_events();
-  const hipEvent_t ev0 = (hipEvent_t)le.start, ev1 = (hipEvent_t)le.stop;
-  const bool timed = ev0 && ev1;
-  le.start = le.stop = nullptr;
-  const bool held = dgp_host::with_kernel_args<TL, GROUP, DOF, IO>(kc, [&](auto k) {
+  hipError_t e = hipErrorInvalidValue;      // (stays: this unit does not hold the kernel)
+  dgp_host::with_kernel_args<TL, GROUP, DOF, IO>(kc, [&](auto k) {
     typedef decltype(k) K;
-    if constexpr (K::MODE == dgp_host::MODE_BACKWARD) {
-      if (timed) hipExtLaunchKernelGGL((gn_backward_kernel<DOF, K::LPT, K::C, IO, K::QK, K::CHAIN>), grid, block, 0, s, ev0, ev1, 0, p, *g);
-      else hipLaunchKernelGGL((gn_backward_kernel<DOF, K::LPT, K::C, IO, K::QK, K::CHAIN>), grid, block, 0, s, p, *g);
-    } else {
-      if (timed) hipExtLaunchKernelGGL((gn_kernel<DOF, K::LPT, K::C, IO, K::MODE, K::QK>), grid, block, 0, s, ev0, ev1, 0, p);
-      else hipLaunchKernelGGL((gn_kernel<DOF, K::LPT, K::C, IO, K::MODE, K::QK>), grid, block, 0, s, p);
-    }
+    if constexpr (K::MODE == dgp_host::MODE_BACKWARD) e = launch(gn_backward_kernel<DOF, K::LPT, K::C, IO, K::QK, K::CHAIN>, grid, block, 0, s, ev, p, *g);
+    else e = launch(gn_kernel<DOF, K::LPT, K::C, IO, K::MODE, K::QK>, grid, block, 0, s, ev, p);
   });
-  return held ? hipGetLastError() : hipErrorInvalidValue;
+  return e;
 }
 
 }  // namespace dgp_dev

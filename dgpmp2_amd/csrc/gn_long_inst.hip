@@ -24,14 +24,10 @@ hipError_t ensure_lds_limit(K kernel) {
 
 template <typename K, typename... A>
 hipError_t launch_dyn(K kernel, int lds_bytes, int B, hipStream_t s, const A&... args) {
+  const dgp_dev::Events ev = dgp_dev::take_events();      // (handed over by HipLaunch in dgpmp2_hip.hip: dgp_launch.h, pass_events)
   hipError_t e = ensure_lds_limit(kernel);
   if (e != hipSuccess) return e;
-  dgp_host::LaunchEvents& le = dgp_host::launch_events();
-  const hipEvent_t ev0 = (hipEvent_t)le.start, ev1 = (hipEvent_t)le.stop;
-  le.start = le.stop = nullptr;
-  if (ev0 && ev1) hipExtLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64), lds_bytes, s, ev0, ev1, 0, args...);
-  else hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64), lds_bytes, s, args...);
-  return hipGetLastError();
+  return dgp_dev::launch(kernel, dim3((unsigned)B), dim3(64), (unsigned)lds_bytes, s, ev, args...);
 }
 
 template <int DOF, typename IO>

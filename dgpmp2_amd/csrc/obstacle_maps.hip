@@ -21,13 +21,16 @@
 //      when they are formed, elements outside [0, W) of a row are masked.
 // No atomics, nothing allocated or synchronised.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
+#include <math.h>
 #include <stdint.h>
-#include "dgp_host.h"
+#include <stdlib.h>
+#include "dgp_launch.h"
+#include "dgp_philox.h"
 
 namespace {
 
 using dgp_host::fail;
+using dgp::philox4x32_10;
 
 constexpr int MAXB = DGP_OBST_MAX_BOXES, MAXP = DGP_OBST_MAX_POINTS, MAXG = DGP_OBST_MAX_GENERATORS;
 constexpr int TPB = 256, WAVES = TPB / 64;
@@ -50,17 +53,6 @@ struct ObstArgs {
 static_assert(sizeof(ObstArgs) <= 4096, "kernel-argument segment");
 
 struct Box { int r0, r1, c0, c1; };      // rows [r0, r1) x columns [c0, c1); empty where r0 >= r1 or c0 >= c1
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // an integer of the inclusive range [a, b] from one word
 __device__ __forceinline__ int draw_in(uint32_t w, int a, int b) { return a + (int)(((uint64_t)w * (uint32_t)(b - a + 1)) >> 32); }
@@ -280,9 +272,7 @@ __global__ void __launch_bounds__(TPB) obstacle_maps_kernel(const ObstArgs a) {
 extern "C" int dgp_obstacle_maps(const DgpHandle* h, int32_t batch, int32_t rows, int32_t cols, const DgpObstacleParams* params, int32_t num_params, uint64_t seed,
                                  uint64_t first_env, const double* start_pts, const double* goal_pts, int32_t num_pts, void* image, int32_t image_dtype,
                                  int32_t* boxes, int32_t* num_boxes, int32_t* draws, int32_t* info, void* stream) {
-  dgp_host::LaunchEvents& le = dgp_host::launch_events();
-  const hipEvent_t ev0 = (hipEvent_t)le.start, ev1 = (hipEvent_t)le.stop;
-  le.start = le.stop = nullptr;
+  const dgp_dev::Events ev = dgp_dev::take_events();
   if (!h) return fail(DGP_EINVAL, "null handle");
   if (!params) return fail(DGP_EINVAL, "dgp_obstacle_maps: null DgpObstacleParams");
   if (!image) return fail(DGP_EINVAL, "dgp_obstacle_maps: image must be a non-null device pointer");
@@ -334,17 +324,8 @@ extern "C" int dgp_obstacle_maps(const DgpHandle* h, int32_t batch, int32_t rows
   a.key0 = (uint32_t)(seed & 0xffffffffu); a.key1 = (uint32_t)(seed >> 32);
   const dim3 grid((unsigned)batch), block(TPB);
   hipStream_t s = (hipStream_t)stream;
-  const bool timed = ev0 && ev1;
-#define DGP_OBST_LAUNCH(T)                                                                              \
-  do {                                                                                                  \
-    if (timed) hipExtLaunchKernelGGL((obstacle_maps_kernel<T>), grid, block, 0, s, ev0, ev1, 0, a);     \
-    else hipLaunchKernelGGL((obstacle_maps_kernel<T>), grid, block, 0, s, a);                           \
-  } while (0)
-  if (image_dtype == DGP_U8) DGP_OBST_LAUNCH(uint8_t);
-  else if (image_dtype == DGP_F32) DGP_OBST_LAUNCH(float);
-  else DGP_OBST_LAUNCH(double);
-#undef DGP_OBST_LAUNCH
-  const hipError_t er = hipGetLastError();
-  if (er != hipSuccess) return fail(DGP_EHIP, "dgp_obstacle_maps launch failed: %s", hipGetErrorString(er));
-  return DGP_OK;
+  const hipError_t er = image_dtype == DGP_U8 ? dgp_dev::launch(obstacle_maps_kernel<uint8_t>, grid, block, 0, s, ev, a)
+                        : (image_dtype == DGP_F32 ? dgp_dev::launch(obstacle_maps_kernel<float>, grid, block, 0, s, ev, a)
+                                                  : dgp_dev::launch(obstacle_maps_kernel<double>, grid, block, 0, s, ev, a));
+  return dgp_dev::hip_rc(er, "dgp_obstacle_maps");
 }

@@ -18,16 +18,18 @@
 // (DGP_TL = 2, this unit's flag: a run-time branch) -- and the distance in the reference's operation order, contraction off; no hinge here: a point is feasible where
 // dist > clearance.  No atomics, nothing allocated or synchronised.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #include <stdint.h>
 #ifndef DGP_TL
 #define DGP_TL 2
 #endif
 #include "dgp_host.h"
+#include "dgp_launch.h"
+#include "dgp_philox.h"
 
 namespace {
 
 using dgp_host::fail;
+using dgp::philox4x32_10;
 
 constexpr int GW = 16;      // lanes per problem
 
@@ -50,17 +52,6 @@ struct SampleArgs {
   double total_time_sec;
 };
 static_assert(sizeof(SampleArgs) <= 4096, "kernel-argument segment");
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // candidate k of `problem` in stream 0 (start) / 1 (goal)
 __device__ __forceinline__ void candidate(const SampleArgs& a, uint64_t problem, uint32_t k, uint32_t stream, double& x, double& y) {
@@ -211,9 +202,7 @@ extern "C" int dgp_sample_problems(const DgpHandle* h, int32_t batch, const DgpS
                                    uint64_t first_problem, const int32_t* diagonal, void* start, void* goal, void* th_init, int32_t* draws, int32_t* info,
                                    void* stream) {
 #pragma clang fp contract(off)
-  dgp_host::LaunchEvents& le = dgp_host::launch_events();
-  const hipEvent_t ev0 = (hipEvent_t)le.start, ev1 = (hipEvent_t)le.stop;
-  le.start = le.stop = nullptr;
+  const dgp_dev::Events ev = dgp_dev::take_events();
   if (!h) return fail(DGP_EINVAL, "null handle");
   if (h->cfg.dof != 2) return fail(DGP_EINVAL, "dgp_sample_problems: only dof == 2 (the reference samples 2-D point-robot problems only), got %d", h->cfg.dof);
   if (!sp) return fail(DGP_EINVAL, "dgp_sample_problems: null DgpSampleParams");
@@ -242,15 +231,7 @@ extern "C" int dgp_sample_problems(const DgpHandle* h, int32_t batch, const DgpS
   a.total_time_sec = c.total_time_sec;
   const dim3 grid((unsigned)((a.p.B + (64 / GW) - 1) / (64 / GW))), block(64);
   hipStream_t s = (hipStream_t)stream;
-  const bool timed = ev0 && ev1;
-  if (c.io_dtype == DGP_F64) {
-    if (timed) hipExtLaunchKernelGGL((sample_problems_kernel<double>), grid, block, 0, s, ev0, ev1, 0, a);
-    else hipLaunchKernelGGL((sample_problems_kernel<double>), grid, block, 0, s, a);
-  } else {
-    if (timed) hipExtLaunchKernelGGL((sample_problems_kernel<float>), grid, block, 0, s, ev0, ev1, 0, a);
-    else hipLaunchKernelGGL((sample_problems_kernel<float>), grid, block, 0, s, a);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(DGP_EHIP, "dgp_sample_problems launch failed: %s", hipGetErrorString(e));
-  return DGP_OK;
+  const hipError_t e = c.io_dtype == DGP_F64 ? dgp_dev::launch(sample_problems_kernel<double>, grid, block, 0, s, ev, a)
+                                             : dgp_dev::launch(sample_problems_kernel<float>, grid, block, 0, s, ev, a);
+  return dgp_dev::hip_rc(e, "dgp_sample_problems");
 }

@@ -21,8 +21,10 @@
 // HBM traffic per padded pixel: image in (once) + 2 x 2 bytes of the words (written by the column pass, read by
 // the row pass; + 4 more bytes in edt_columns) + the field out; no arithmetic to speak of -- an HBM-bound byte kernel, not MFMA work.
 #include <hip/hip_runtime.h>
+#include <math.h>
+#include <stddef.h>
 #include <stdint.h>
-#include "dgp_host.h"
+#include "dgp_status.h"
 
 namespace {
 

@@ -15,12 +15,12 @@
 // depends on n and LPT only: no atomics, bit-identical results from run to run and wherever the trajectory sits in the batch.  Lanes 0 .. 12 of a trajectory store its
 // DGP_METRIC_COUNT doubles as one contiguous run.  Lane groups past the end of a ragged batch recompute the last trajectory and store nothing (no divergent shuffles).
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #include <stdint.h>
 #ifndef DGP_TL
 #define DGP_TL 2
 #endif
 #include "dgp_host.h"
+#include "dgp_launch.h"
 
 namespace {
 
@@ -151,29 +151,19 @@ __global__ void __launch_bounds__(64) traj_metrics_kernel(const MetricsArgs a) {
 }
 
 template <int DOF, typename IO>
-void launch_lpt(int lpt, const MetricsArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+hipError_t launch_lpt(int lpt, const MetricsArgs& a, hipStream_t s, const dgp_dev::Events& ev) {
   const int tpw = 64 / lpt;
   const dim3 grid((unsigned)((a.p.B + tpw - 1) / tpw)), block(64);
-  const bool timed = ev0 && ev1;
-#define DGP_METRICS_LAUNCH(L)                                                                                   \
-  do {                                                                                                          \
-    if (timed) hipExtLaunchKernelGGL((traj_metrics_kernel<DOF, IO, L>), grid, block, 0, s, ev0, ev1, 0, a);     \
-    else hipLaunchKernelGGL((traj_metrics_kernel<DOF, IO, L>), grid, block, 0, s, a);                           \
-  } while (0)
-  if (lpt == 16) DGP_METRICS_LAUNCH(16);
-  else if (lpt == 32) DGP_METRICS_LAUNCH(32);
-  else DGP_METRICS_LAUNCH(64);
-#undef DGP_METRICS_LAUNCH
+  if (lpt == 16) return dgp_dev::launch(traj_metrics_kernel<DOF, IO, 16>, grid, block, 0, s, ev, a);
+  if (lpt == 32) return dgp_dev::launch(traj_metrics_kernel<DOF, IO, 32>, grid, block, 0, s, ev, a);
+  return dgp_dev::launch(traj_metrics_kernel<DOF, IO, 64>, grid, block, 0, s, ev, a);
 }
 
 }  // namespace
 
 extern "C" int dgp_traj_metrics(const DgpHandle* h, int32_t batch, const void* th, const DgpSdf* sdf, double metric_eps, const void* th_opt,
                                 double* metrics, void* obs_error, void* stream) {
-  // dgp_time_next_launch(): one-shot; a call that fails validation launches nothing and must not leave the request to an unrelated later launch
-  dgp_host::LaunchEvents& le = dgp_host::launch_events();
-  const hipEvent_t ev0 = (hipEvent_t)le.start, ev1 = (hipEvent_t)le.stop;
-  le.start = le.stop = nullptr;
+  const dgp_dev::Events ev = dgp_dev::take_events();
   MetricsArgs a;
   const int rc = dgp_host::fill_call(h, batch, th, /*start=*/th, /*goal=*/th, sdf, nullptr, a.p);      // (no start / goal here: th stands in for the null checks)
   if (rc != DGP_OK) return rc;
@@ -184,9 +174,7 @@ extern "C" int dgp_traj_metrics(const DgpHandle* h, int32_t batch, const void* t
   const int lpt = a.p.n <= 64 ? 16 : (a.p.n <= 128 ? 32 : 64);
   hipStream_t s = (hipStream_t)stream;
   const bool f64 = h->cfg.io_dtype == DGP_F64;
-  if (h->cfg.dof == 2) { if (f64) launch_lpt<2, double>(lpt, a, s, ev0, ev1); else launch_lpt<2, float>(lpt, a, s, ev0, ev1); }
-  else { if (f64) launch_lpt<3, double>(lpt, a, s, ev0, ev1); else launch_lpt<3, float>(lpt, a, s, ev0, ev1); }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(DGP_EHIP, "dgp_traj_metrics launch failed: %s", hipGetErrorString(e));
-  return DGP_OK;
+  const hipError_t e = h->cfg.dof == 2 ? (f64 ? launch_lpt<2, double>(lpt, a, s, ev) : launch_lpt<2, float>(lpt, a, s, ev))
+                                       : (f64 ? launch_lpt<3, double>(lpt, a, s, ev) : launch_lpt<3, float>(lpt, a, s, ev));
+  return dgp_dev::hip_rc(e, "dgp_traj_metrics");
 }

@@ -215,62 +215,45 @@ int emul_time_next_launch(void*, void*) { return DGP_OK; }      // nothing to ti
 int emul_launch_shape(const DgpHandle* h, int32_t batch, int32_t* lpt, int32_t* c) { return dgp_host::launch_shape(h, batch, lpt, c); }
 int emul_step_kernel_variant(const DgpHandle* h, int32_t batch) { return dgp_host::step_kernel_variant(h, batch); }
 
-int emul_gn_step(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
-                 const DgpCovs* covs, void* dtheta, void* err, void* err_ext, int32_t* info, void*) {
-  dgp::GnParams p;
-  int rc = dgp_host::fill_step(h, batch, th, start, goal, sdf, covs, dtheta, err, err_ext, info, p);
-  if (rc != DGP_OK) return rc;
-  return run(h, p, nullptr, dgp_host::MODE_STEP);
-}
-
-int emul_gn_solve(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf,
-                  const DgpCovs* covs, int32_t max_iters, double tol_delta, void* th_out, int32_t* iters, void* err_hist,
-                  void* errext_hist, void* err_final, int32_t* info, void*) {
-  dgp::GnParams p;
-  int rc = dgp_host::fill_solve(h, batch, th_init, start, goal, sdf, covs, max_iters, tol_delta, th_out, iters, err_hist,
-                                errext_hist, err_final, info, p);
-  if (rc != DGP_OK) return rc;
-  return run(h, p, nullptr, dgp_host::MODE_SOLVE);
-}
-
-int emul_eval_errors(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
-                     const DgpCovs* covs, void* err, void* err_ext, void* unw_sg, void* unw_gp, void* unw_obs, void*) {
-  dgp::GnParams p;
-  int rc = dgp_host::fill_eval(h, batch, th, start, goal, sdf, covs, err, err_ext, unw_sg, unw_gp, unw_obs, p);
-  if (rc != DGP_OK) return rc;
-  return run(h, p, nullptr, dgp_host::MODE_EVAL);
-}
-
-int emul_gn_step_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
-                          const DgpCovs* covs, const void* dtheta, const void* g_dtheta, const void* g_err_ext, void* g_th,
-                          void* g_start, void* g_goal, void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies, void* g_qc_inv,
-                          void* g_obs_w, void* g_eps, void*) {
-  dgp::GnParams p;
-  dgp::GnGradParams g;
-  int rc = dgp_host::fill_backward(h, batch, th, start, goal, sdf, covs, dtheta, g_dtheta, g_err_ext, g_th, g_start, g_goal, g_sdf,
-                                   g_sdf_batch_stride, g_sdf_copies, g_qc_inv, g_obs_w, g_eps, p, g);
-  if (rc != DGP_OK) return rc;
-  return run(h, p, &g, dgp_host::MODE_BACKWARD);
-}
-
-int emul_eval_errors_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
-                              const DgpCovs* covs, const void* g_err_ext, const void* g_unw_sg, const void* g_unw_gp, const void* g_unw_obs,
-                              void* g_th, void* g_start, void* g_goal, void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies,
-                              void* g_eps, void*) {
-  dgp::GnParams p;
-  dgp::GnGradParams g;
-  int rc = dgp_host::fill_eval_backward(h, batch, th, start, goal, sdf, covs, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start, g_goal,
-                                        g_sdf, g_sdf_batch_stride, g_sdf_copies, g_eps, p, g);
-  if (rc != DGP_OK) return rc;
-  return run(h, p, &g, dgp_host::MODE_BACKWARD);
-}
-
+// the entry points that launch lane programs: dgp_host.h's host logic over the emulator's `run`
 namespace {
 struct EmulLaunch {
   const DgpHandle* h;
   int operator()(int mode, const dgp::GnParams& p, const dgp::GnGradParams* g) const { return run(h, p, g, mode); }
 };
 }  // namespace
+
+int emul_gn_step(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
+                 const DgpCovs* covs, void* dtheta, void* err, void* err_ext, int32_t* info, void*) {
+  return dgp_host::gn_step(h, batch, th, start, goal, sdf, covs, dtheta, err, err_ext, info, EmulLaunch{h});
+}
+
+int emul_gn_solve(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf,
+                  const DgpCovs* covs, int32_t max_iters, double tol_delta, void* th_out, int32_t* iters, void* err_hist,
+                  void* errext_hist, void* err_final, int32_t* info, void*) {
+  return dgp_host::gn_solve(h, batch, th_init, start, goal, sdf, covs, max_iters, tol_delta, th_out, iters, err_hist, errext_hist, err_final, info, EmulLaunch{h});
+}
+
+int emul_eval_errors(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
+                     const DgpCovs* covs, void* err, void* err_ext, void* unw_sg, void* unw_gp, void* unw_obs, void*) {
+  return dgp_host::eval_errors(h, batch, th, start, goal, sdf, covs, err, err_ext, unw_sg, unw_gp, unw_obs, EmulLaunch{h});
+}
+
+int emul_gn_step_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
+                          const DgpCovs* covs, const void* dtheta, const void* g_dtheta, const void* g_err_ext, void* g_th,
+                          void* g_start, void* g_goal, void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies, void* g_qc_inv,
+                          void* g_obs_w, void* g_eps, void*) {
+  return dgp_host::gn_step_backward(h, batch, th, start, goal, sdf, covs, dtheta, g_dtheta, g_err_ext, g_th, g_start, g_goal, g_sdf, g_sdf_batch_stride,
+                                    g_sdf_copies, g_qc_inv, g_obs_w, g_eps, EmulLaunch{h});
+}
+
+int emul_eval_errors_backward(const DgpHandle* h, int32_t batch, const void* th, const void* start, const void* goal, const DgpSdf* sdf,
+                              const DgpCovs* covs, const void* g_err_ext, const void* g_unw_sg, const void* g_unw_gp, const void* g_unw_obs,
+                              void* g_th, void* g_start, void* g_goal, void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies,
+                              void* g_eps, void*) {
+  return dgp_host::eval_errors_backward(h, batch, th, start, goal, sdf, covs, g_err_ext, g_unw_sg, g_unw_gp, g_unw_obs, g_th, g_start, g_goal, g_sdf,
+                                        g_sdf_batch_stride, g_sdf_copies, g_eps, EmulLaunch{h});
+}
 
 int emul_gn_solve_traced(const DgpHandle* h, int32_t batch, const void* th_init, const void* start, const void* goal, const DgpSdf* sdf,
                          const DgpCovs* covs, int32_t max_iters, double tol_delta, void* th_out, int32_t* iters, void* err_hist,

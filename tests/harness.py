@@ -17,7 +17,7 @@ EMUL_LIB = os.path.join(EMUL_DIR, 'libgn_emul.so')
 
 def build_emulator(force=False):
   src = os.path.join(EMUL_DIR, 'emul_main.cpp')
-  deps = [src] + [os.path.join(ROOT, 'dgpmp2_amd', 'csrc', f) for f in ('gn_lane.h', 'gn_woodbury.h', 'gn_backward.h', 'gn_long.h', 'dgp_host.h')] + \
+  deps = [src] + [os.path.join(ROOT, 'dgpmp2_amd', 'csrc', f) for f in ('gn_lane.h', 'gn_woodbury.h', 'gn_backward.h', 'gn_long.h', 'dgp_status.h', 'dgp_host.h')] + \
          [os.path.join(ROOT, 'include', 'dgpmp2_hip.h')]
   # DGP_EMUL_CXX / DGP_EMUL_LIB (profiles/tools/r06_emul_sanitize.sh): another compiler and output name -- the sanitizer / poisoned-stack builds of the lane program
   lib = os.environ.get('DGP_EMUL_LIB', EMUL_LIB)

@@ -107,6 +107,12 @@ def test_entry_point_validates_arguments_without_gpu():
   # a request of dgp_time_next_launch does not survive a rejected call
   assert api.time_next_launch(0x10, 0x20) == _capi.DGP_OK
   assert code(0, 0x1000, ok, metrics=0x1000) == _capi.DGP_EINVAL
+  # ... whichever translation unit rejects it: the solver's entry points, the problem sampler, the obstacle-map generator (null handle)
+  for call in (lambda: api.gn_step(None, 8, 0x1000, 0x1000, 0x1000, ok, None, 0x1000, None, None, None, None),
+               lambda: api.sample_problems(None, 8, ok, None, None, 1, 0, None, 0x1000, 0x1000, 0x1000, None, None, None),
+               lambda: api.obstacle_maps(None, 2, 32, 32, None, 1, 1, 0, None, None, 0, 0x1000, _capi.DGP_U8, None, None, None, None, None)):
+    assert api.time_next_launch(0x10, 0x20) == _capi.DGP_OK
+    assert call() == _capi.DGP_EINVAL and b'null handle' in api.last_error()
   assert api.time_next_launch(None, None) == _capi.DGP_OK
 
 
