@@ -60,6 +60,10 @@ class DgpObstacleParams(C.Structure):
               ('patch_size_obs', C.c_double), ('patch_size', C.c_double)]
 
 
+class DgpPathParams(C.Structure):
+  _fields_ = [('clearance', C.c_double), ('max_sweeps', C.c_int32), ('path_cap', C.c_int32)]
+
+
 class DgpError(RuntimeError):
   def __init__(self, code, msg):
     super(DgpError, self).__init__('dgpmp2_hip error %d: %s' % (code, msg))
@@ -71,7 +75,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -134,6 +138,11 @@ class CApi(object):
     if self.obstacle_maps is not None:
       self.obstacle_maps.restype = C.c_int
       self.obstacle_maps.argtypes = [vp, i32, i32, i32, C.POINTER(DgpObstacleParams), i32, C.c_uint64, C.c_uint64, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    # dgp_init_paths: no twin in the emulator either
+    self.init_paths = getattr(self.lib, prefix + 'init_paths', None)
+    if self.init_paths is not None:
+      self.init_paths.restype = C.c_int
+      self.init_paths.argtypes = [vp, i32, C.POINTER(DgpSdf), vp, C.POINTER(DgpPathParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     self.time_next_launch = f('time_next_launch'); self.time_next_launch.restype = C.c_int; self.time_next_launch.argtypes = [vp, vp]
     self.event_create = f('event_create'); self.event_create.restype = C.c_int; self.event_create.argtypes = [C.POINTER(vp)]
     self.event_destroy = f('event_destroy'); self.event_destroy.restype = None; self.event_destroy.argtypes = [vp]
@@ -411,6 +420,20 @@ class Solver(object):
       arr = (DgpObstacleParams * max(n, 1))(*params)
     self.api.check(self.api.obstacle_maps(self.handle, int(batch), int(rows), int(cols), arr, n, int(seed), int(first_env), start_pts, goal_pts, int(num_pts), image,
                                           int(image_dtype), boxes, num_boxes, draws, info, stream))
+
+  @staticmethod
+  def path_params(clearance, max_sweeps=64, path_cap=0):
+    """DgpPathParams: a cell is free where its stored distance exceeds `clearance` (the reference's RRT* validity: sphere_radius + epsilon_dist, ompl_rrtstar.py:18);
+    max_sweeps bounds the sweeps of the distance field, path_cap is the second dimension of path_cells."""
+    return DgpPathParams(float(clearance), int(max_sweeps), int(path_cap))
+
+  def init_paths(self, batch, sdf, params, start, goal, th_init, field, env_index=None, path_cells=None, num_cells=None, length=None, info=None, stream=None):
+    """dgp_init_paths: th_init (B,n,4) of the I/O type from start / goal (B,1,4); field (B,H,W) uint32 (workspace and output); path_cells (B,path_cap), num_cells (B)
+    and info (B) int32, length (B) float64; one launch."""
+    if self.api.init_paths is None:
+      raise NotImplementedError('%s does not export %sinit_paths (the CPU emulator has no twin of the path kernel)' % (self.api.path, self.api.prefix))
+    self.api.check(self.api.init_paths(self.handle, batch, C.byref(sdf) if sdf is not None else None, env_index, C.byref(params) if params is not None else None,
+                                       start, goal, th_init, field, path_cells, num_cells, length, info, stream))
 
   def eval_errors_backward(self, batch, th, start, goal, sdf, covs, g_err_ext=None, g_unw_sg=None, g_unw_gp=None, g_unw_obs=None,
                            g_th=None, g_start=None, g_goal=None, g_sdf=None, g_sdf_batch_stride=0, g_eps=None, stream=None, g_sdf_copies=1):

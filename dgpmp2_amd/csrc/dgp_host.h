@@ -19,6 +19,7 @@ struct DgpHandle {
   int force_lpt, force_c;   // >0: launch shape pinned by the environment variable DGP_FORCE_SHAPE="LPT,C" (tuning aid)
   dgp::GnParams base;   // constants filled once
 };
+static_assert(__builtin_offsetof(DgpHandle, cfg) == 0, "init_paths.hip reads the configuration through the handle's address: cfg stays the first member");
 
 // Launch shape: LPT lanes per trajectory x C consecutive states per lane, LPT*C >= n.
 struct DgpShape { int lpt, c; };

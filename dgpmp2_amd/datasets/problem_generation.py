@@ -5,7 +5,8 @@ images -> SDFs -> feasible start / goal pairs -> straight-line initial trajector
 Python rejection loops, one Env2D.is_feasible call per candidate point; here every problem of a batch is sampled by ONE launch (dgp_sample_problems,
 csrc/problem_sampler.hip) with counter-based randomness: problem number p of a seed is the same problem whatever batch it is drawn in.  The images are an input, or
 made on the device as well (datasets/obstacle_maps.py, dgp_obstacle_maps: the reference's obst_generator.py): generate_dataset then starts from a seed.  RRT*
-initialisation (OMPL) and plotting are not part of this build.
+itself (OMPL) and plotting are not part of this build; the role of the reference's --rrt_star_init -- an initial trajectory that is collision-free where the straight
+line is not -- is taken by init_paths (dgp_init_paths, csrc/init_paths.hip): the 5-7 shortest grid path through the free cells, resampled to n states.
 """
 import numpy as np
 import torch
@@ -33,11 +34,81 @@ class SampleInfo(object):
   def diagonal_replaced(self): return (self.flags & INFO_DIAGONAL_REPLACED) != 0
 
 
+INFO_START_BLOCKED, INFO_GOAL_BLOCKED, INFO_UNREACHABLE, INFO_UNCONVERGED, INFO_PATH_TRUNCATED = 1, 2, 4, 8, 16      # bits of dgp_init_paths' `info`
+_FIELD_SCRATCH_BYTES = 1 << 30      # init_paths without return_field: the uint32 distance fields of one launch stay at or below this
+
+
+class PathInfo(object):
+  """What dgp_init_paths reports per problem, device tensors: `flags` (B,) int32 of INFO_* bits, `num_cells` (B,) int32 (cells of the traced path; 0 for a fallback),
+  `length` (B,) float64 (arc length of the polyline start -> cells -> goal; the straight distance for a fallback), `path_cells` (B,path_cap) int32 (r * W + c of
+  the traced cells, -1 behind them) or None when path_cap is 0, `field` (B,H,W) int32 or None: the BITS of the uint32 cost-to-go field (5 per axis move, 7 per
+  diagonal; -1 = 0xffffffff: blocked or unreached) when it was asked for."""
+  __slots__ = ('flags', 'num_cells', 'length', 'path_cells', 'field')
+
+  def __init__(self, flags, num_cells, length, path_cells=None, field=None):
+    self.flags, self.num_cells, self.length, self.path_cells, self.field = flags, num_cells, length, path_cells, field
+
+  @property
+  def fell_back(self): return (self.flags & (INFO_START_BLOCKED | INFO_GOAL_BLOCKED | INFO_UNREACHABLE | INFO_UNCONVERGED)) != 0      # th_init is the straight line
+
+  @property
+  def unreachable(self): return (self.flags & INFO_UNREACHABLE) != 0
+
+  @property
+  def unconverged(self): return (self.flags & INFO_UNCONVERGED) != 0
+
+
 def _layer(planner_or_layer):
   return getattr(planner_or_layer, 'plan_layer', planner_or_layer)
 
 
-def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, clearance=None, seed=0, first_problem=0, diagonal=None, dtype=None, **params):
+def init_paths(planner_or_layer, sdfb, startb, goalb, env_index=None, clearance=None, max_sweeps=64, path_cap=0, return_field=False, dtype=None):
+  """Collision-free initial trajectories for a batch of problems, on the device: for every (start, goal) pair the 5-7 shortest path through the free cells of its
+  grid, resampled to n states at equal arc length, with the constant velocities of the reference's path_to_traj_avg_vel -- the role of --rrt_star_init
+  (generate_optimal_paths_gpmp2.py:95-110).  include/dgpmp2_hip.h states the exact rule.
+  sdfb: ROW-MAJOR grids as forward() takes them -- (E,1,H,W) / (E,H,W), or a shared (1,1,H,W) / expand()ed grid; a host tensor raises, and so does a TiledSdf
+  (untile_sdf gives the row-major grids back).  startb, goalb (B,1,4).  env_index (B,) integer device tensor: the grid of each problem (checked like sample_problems').
+  clearance: a cell is free where its stored distance exceeds it; default sphere_radius + epsilon_dist (ompl_rrtstar.py:18).  max_sweeps bounds the sweeps of the
+  distance field (a problem that needs more falls back and is flagged), path_cap > 0 asks for the traced cells, return_field for the (B,H,W) distance fields.
+  Without return_field the batch runs in chunks whose uint32 fields stay at or below 1 GiB; a problem's result does not depend on its position or batch, so
+  chunking changes nothing.  Problems that fall back (info.fell_back) get the straight line of sample_problems.
+  -> (th_initb (B,n,4), info: PathInfo), device tensors."""
+  layer = _layer(planner_or_layer)
+  if not torch.is_tensor(sdfb) or not sdfb.is_cuda:
+    raise RuntimeError('dgpmp2_amd.init_paths: `sdfb` must be a CUDA/ROCm tensor; this build has no CPU path')
+  for name, t in (('startb', startb), ('goalb', goalb)):
+    if not torch.is_tensor(t) or not t.is_cuda: raise RuntimeError('dgpmp2_amd.init_paths: `%s` must be a CUDA/ROCm tensor; this build has no CPU path' % name)
+  if sdfb.dim() == 6:
+    raise ValueError('dgpmp2_amd.init_paths reads row-major grids, not 4 x 4 tiles (TiledSdf): pass utils.sdf_utils.untile_sdf(sdfb) or the row-major tensor')
+  if sdfb.dim() == 3: sdfb = sdfb.unsqueeze(1)
+  if dtype is None: dtype = sdfb.dtype
+  if clearance is None:
+    from ..gpmp2.plan_layer import _f
+    clearance = _f(layer.robot_model.get_sphere_radii()) + _f(layer.obs_params['epsilon_dist'])
+  pp = _capi.Solver.path_params(clearance, max_sweeps, path_cap)
+  grids, B = int(sdfb.shape[0]), int(startb.shape[0])
+  shared = grids == 1 or sdfb.stride(0) == 0
+  if env_index is not None:
+    env_index = env_index.to(torch.int32)
+    if not shared and env_index.is_cuda and not torch.cuda.is_current_stream_capturing():
+      lo, hi = torch.aminmax(env_index)
+      if int(lo) < 0 or int(hi) >= grids: raise ValueError('env_index must lie in [0, %d), got values in [%d, %d]' % (grids, int(lo), int(hi)))
+  H, W = int(sdfb.shape[-2]), int(sdfb.shape[-1])
+  chunk = B if return_field else max(1, min(B, _FIELD_SCRATCH_BYTES // (4 * H * W)))
+  if chunk >= B:
+    th, field, cells, num, length, flags = layer.init_paths(sdfb, startb, goalb, pp, dtype, env_index)
+    return th, PathInfo(flags, num, length, cells if path_cap > 0 else None, field if return_field else None)
+  parts, scratch = [], torch.empty((chunk, H, W), dtype=torch.int32, device=sdfb.device)
+  for b0 in range(0, B, chunk):
+    b1 = min(B, b0 + chunk)
+    grid = sdfb if (shared or env_index is not None) else sdfb[b0:b1]
+    parts.append(layer.init_paths(grid, startb[b0:b1], goalb[b0:b1], pp, dtype, None if env_index is None else env_index[b0:b1], scratch[:b1 - b0]))
+  th, cells, num, length, flags = (torch.cat([p[i] for p in parts]) for i in (0, 2, 3, 4, 5))
+  return th, PathInfo(flags, num, length, cells if path_cap > 0 else None, None)
+
+
+def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, clearance=None, seed=0, first_problem=0, diagonal=None, dtype=None, init='straight',
+                    **params):
   """Feasible start / goal pairs and straight-line initial trajectories for `num_problems` planning problems, one launch.
   planner_or_layer: a DiffGPMP2Planner or its PlanLayer (dof 2).  sdfb: the signed distance fields as forward() takes them -- (E,1,H,W) (or (E,H,W), what sdf_2d_batch
   returns), a utils.sdf_utils.TiledSdf, or a shared (1,1,H,W) / expand()ed grid; a host tensor raises, like sdf_2d_batch.  num_problems: default one per grid.
@@ -45,6 +116,8 @@ def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, c
   number of grids (one small device -> host copy; not under HIP-graph capture, where the caller vouches for them).  clearance: a point is feasible where its signed
   distance exceeds it; default sphere_radius + epsilon_dist + 0.1 (generate_optimal_paths_gpmp2.py:124).  (seed, first_problem + b) determine problem b.
   diagonal (B,) integer device tensor: -1 random, 0..3 the corner-to-corner problem of :134-145.  dtype: of the outputs, default that of sdfb.
+  init: 'straight' (the straight lines of the launch itself) or 'grid_path': th_initb is init_paths' for the pairs just sampled, at its default clearance (row-major
+  grids only).
   **params: margin (0.5), min_dist_frac (0.6), near_tries (15), max_draws (4096), corner_inset (0.2) -- _capi.DgpSampleParams.
   -> (startb (B,1,4), goalb (B,1,4), th_initb (B,n,4), info: SampleInfo), device tensors."""
   layer = _layer(planner_or_layer)
@@ -65,25 +138,29 @@ def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, c
       lo, hi = torch.aminmax(env_index)
       if int(lo) < 0 or int(hi) >= grids: raise ValueError('env_index must lie in [0, %d), got values in [%d, %d]' % (grids, int(lo), int(hi)))
   if diagonal is not None: diagonal = diagonal.to(torch.int32)
+  if init not in ('straight', 'grid_path'): raise ValueError("init must be 'straight' or 'grid_path', got %r" % (init,))
   startb, goalb, th_initb, draws, info = layer.sample_problems(sdfb, B, sp, dtype, env_index, diagonal, seed, first_problem)
+  if init == 'grid_path': th_initb = init_paths(layer, sdfb, startb, goalb, env_index=env_index, dtype=dtype)[0]
   return startb, goalb, th_initb, SampleInfo(info, draws)
 
 
 def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, first_diagonal=True, require_collision_free=True, dataset_type=None, num_envs=None,
-                     im_size=None, obstacle_params=None, **params):
+                     im_size=None, obstacle_params=None, init='straight', **params):
   """The reference's generation chain for a batch of environments, on the device until the files are written:
     0. images=None: generate_obstacle_maps(planner, dataset_type, num_envs, im_size, seed=seed, **obstacle_params) makes the images (uint8); an environment whose
        map is flagged capped or overlapping is dropped before anything else runs           (generate_2d_dataset.py:194-208; the reference never returns such a map)
     1. sdf_2d_batch(images, padlen=0, res=cell_size)                              (generate_2d_dataset.py:211; cell_size = (x_max - x_min) / image width)
     2. sample_problems: probs_per_env problems per environment; with first_diagonal the first problem of every environment is one of the four diagonals, drawn
        from `seed`                                                                (generate_optimal_paths_gpmp2.py:126-148)
-    3. planner.forward on the straight-line initial trajectories                  (:181-184)
+    3. planner.forward on the initial trajectories: the straight lines (init='straight'), or init_paths' collision-free grid paths (init='grid_path': the
+       reference's --rrt_star_init switch, :95-110, :156-159; generate_2d_dataset.py:225-226)                                                   (:181-184)
     4. trajectory_metrics(eps=0): in_coll of every planned trajectory             (generate_2d_dataset.py:247-252)
     5. write_environment / write_problem / write_meta
   images: (E,H,W) or (E,1,H,W) device tensor, free space > 0.75.  An environment with a problem whose sampling hit max_draws is dropped; so is one with a planned
   trajectory in collision when require_collision_free is set (the reference drops an environment by exception, :247-265).  Written environments are numbered densely.
   **params go to sample_problems.  -> {'num_envs': written, 'kept': [input indices], 'dropped': {input index: reason}, 'start', 'goal', 'th_init', 'th_opt': device
-  tensors of ALL E * probs_per_env problems (problem e * probs_per_env + j), 'info': SampleInfo, 'in_coll': (E * probs_per_env,) bool}.  With images=None, 'kept' and
+  tensors of ALL E * probs_per_env problems (problem e * probs_per_env + j), 'info': SampleInfo, 'in_coll': (E * probs_per_env,) bool, 'path_info': the PathInfo of
+  init_paths (None with init='straight')}.  With images=None, 'kept' and
   'dropped' count in the num_envs generated environments, E is the number of them that went through the chain, and 'images' (E,1,H,W), 'env_numbers' (their numbers
   among the generated ones) and 'obstacle_info' (ObstacleInfo of all num_envs) are returned as well."""
   from ..utils.sdf_utils import sdf_2d_batch
@@ -94,10 +171,11 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
     capped_h, over_h = oinfo.capped.cpu().numpy(), oinfo.overlapping.cpu().numpy()
     good = [e for e in range(int(num_envs)) if not (capped_h[e] or over_h[e])]
     sel = torch.tensor(good, dtype=torch.long, device=gen.device)
-    r = {'num_envs': 0, 'kept': [], 'dropped': {}}
+    if init not in ('straight', 'grid_path'): raise ValueError("init must be 'straight' or 'grid_path', got %r" % (init,))
+    r = {'num_envs': 0, 'kept': [], 'dropped': {}, 'path_info': None}
     if good:
       r = generate_dataset(root_dir, mode, gen[sel], planner, probs_per_env, seed=seed, first_diagonal=first_diagonal,
-                           require_collision_free=require_collision_free, **params)
+                           require_collision_free=require_collision_free, init=init, **params)
     else:
       write_meta(root_dir, mode, 0, int(probs_per_env), {'x_lims': [float(v) for v in planner.env_params['x_lims']], 'y_lims': [float(v) for v in planner.env_params['y_lims']]},
                  int(gen.shape[-1]))
@@ -109,6 +187,7 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
     r.update(images=gen[sel], env_numbers=good, obstacle_info=oinfo)
     return r
   if not torch.is_tensor(images) or not images.is_cuda: raise RuntimeError('dgpmp2_amd.generate_dataset: `images` must be a CUDA/ROCm tensor; this build has no CPU path')
+  if init not in ('straight', 'grid_path'): raise ValueError("init must be 'straight' or 'grid_path', got %r" % (init,))
   layer = planner.plan_layer
   im = images[:, 0] if images.dim() == 4 else images
   E, H, W = im.shape
@@ -121,6 +200,8 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
   diagonal = torch.full((B,), -1, dtype=torch.int32, device=im.device)
   if first_diagonal: diagonal[::P] = torch.from_numpy(np.random.RandomState(seed).randint(0, 4, E).astype(np.int32)).to(im.device)
   startb, goalb, th_initb, info = sample_problems(layer, sdf, B, env_index=env_index, seed=seed, diagonal=diagonal, **params)
+  path_info = None
+  if init == 'grid_path': th_initb, path_info = init_paths(layer, sdf, startb, goalb, env_index=env_index)
   sdfb = sdf.index_select(0, env_index.long())      # one grid per problem, what forward() takes
   imb = (im > 0.75).to(sdf.dtype).unsqueeze(1).index_select(0, env_index.long())
   with torch.no_grad():
@@ -142,4 +223,4 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
       kept.append(e)
   write_meta(root_dir, mode, len(kept), P, {'x_lims': x_lims, 'y_lims': y_lims}, W)
   return {'num_envs': len(kept), 'kept': kept, 'dropped': dropped, 'start': startb, 'goal': goalb, 'th_init': th_initb, 'th_opt': th_opt, 'info': info,
-          'in_coll': in_coll}
+          'in_coll': in_coll, 'path_info': path_info}

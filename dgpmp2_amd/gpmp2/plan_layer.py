@@ -1116,6 +1116,51 @@ class PlanLayer(nn.Module):
             th_initb.data_ptr(), draws.data_ptr(), info.data_ptr(), _raw_stream(dev))
     return startb, goalb, th_initb, draws, info
 
+  def init_paths(self, sdfb, startb, goalb, params, dtype=torch.float64, env_index=None, field=None):
+    """Collision-free initial trajectories from startb to goalb in ONE launch (dgp_init_paths; datasets.problem_generation.init_paths is the documented front end, fills
+    `params`, a _capi.DgpPathParams, and chunks a large batch).  sdfb: ROW-MAJOR grids as for forward() (per sample, a shared grid, or several addressed through
+    env_index (B) int32); startb / goalb (B,1,4).  field: a (B,H,W) int32 device tensor to use as the distance-field workspace (the bits of the uint32 field), or None.
+    -> th_initb (B,n,4) of `dtype`, field (B,H,W) int32, path_cells (B,path_cap) int32, num_cells (B) int32, length (B) float64, info (B) int32."""
+    if sdfb is None: raise ValueError('init_paths needs the signed-distance grids (sdfb)')
+    _require_cuda(sdfb, 'sdfb')
+    if sdfb.dim() == 6: raise ValueError('init_paths reads row-major grids: untile a TiledSdf first (utils.sdf_utils.untile_sdf)')
+    B, dev = int(startb.shape[0]), sdfb.get_device()
+    for name, t in (('startb', startb), ('goalb', goalb)):
+      _require_cuda(t, name)
+      if t.get_device() != dev: _same_device(dev, **{name: t})
+      if tuple(t.shape) != (B, 1, 4): raise ValueError('%s must be (B,1,4), got %s' % (name, tuple(t.shape)))
+    solver = self._solvers.get(dtype) or self._solver(dtype)
+    grids = int(sdfb.shape[0])
+    shared = grids == 1 or sdfb.stride(0) == 0
+    if env_index is None and not shared and grids != B:
+      raise ValueError('sdfb has %d grids for %d problems: pass env_index (the grid of each problem)' % (grids, B))
+    sd = self._sdf_args(sdfb, dtype, B if (shared or env_index is None) else grids, dev)
+    ei = None
+    if env_index is not None:
+      _require_cuda(env_index, 'env_index')
+      if env_index.get_device() != dev: _same_device(dev, env_index=env_index)
+      if env_index.dtype is not torch.int32 or env_index.dim() != 1 or env_index.shape[0] != B:
+        raise ValueError('env_index must be an int32 tensor of shape (%d,), got %s %s' % (B, env_index.dtype, tuple(env_index.shape)))
+      ei = env_index.contiguous()
+    H, W = int(sd[1]), int(sd[2])
+    device = sdfb.device
+    st, go = startb.detach().to(dtype).contiguous(), goalb.detach().to(dtype).contiguous()
+    if field is None: field = torch.empty((B, H, W), dtype=torch.int32, device=device)
+    elif tuple(field.shape) != (B, H, W) or field.dtype is not torch.int32 or not field.is_contiguous() or field.get_device() != dev:
+      raise ValueError('field must be a contiguous (%d,%d,%d) int32 tensor on the device of sdfb' % (B, H, W))
+    th_initb = torch.empty((B, self.num_traj_states, 4), dtype=dtype, device=device)
+    cap = int(params.path_cap)
+    path_cells = torch.empty((B, cap), dtype=torch.int32, device=device)
+    num_cells = torch.empty((B,), dtype=torch.int32, device=device)
+    info = torch.empty((B,), dtype=torch.int32, device=device)
+    length = torch.empty((B,), dtype=torch.float64, device=device)
+    import ctypes
+    api = _capi.get_api()
+    arg = _capi.DgpSdf(*sd[:7])
+    _launch(dev, api.init_paths, solver.h, B, ctypes.byref(arg), _ptr(ei), ctypes.byref(params), st.data_ptr(), go.data_ptr(), th_initb.data_ptr(), field.data_ptr(),
+            path_cells.data_ptr() if cap > 0 else None, num_cells.data_ptr(), length.data_ptr(), info.data_ptr(), _raw_stream(dev))
+    return th_initb, field, path_cells, num_cells, length, info
+
 
 class TrajectoryMetrics(object):
   """Result of PlanLayer.trajectory_metrics: `raw` is the (B, DGP_METRIC_COUNT) float64 device tensor dgp_traj_metrics wrote (columns _capi.METRIC_NAMES),

@@ -441,6 +441,57 @@ int dgp_obstacle_maps(const DgpHandle* h, int32_t batch, int32_t rows, int32_t c
                       uint64_t first_env, const double* start_pts, const double* goal_pts, int32_t num_pts, void* image, int32_t image_dtype,
                       int32_t* boxes, int32_t* num_boxes, int32_t* draws, int32_t* info, void* stream);
 
+/* Collision-free initial trajectories on the device, ONE launch: for every problem of the batch a trajectory of n states from the start to the goal that stays in
+ * free space -- the role of the reference's --rrt_star_init (datasets/generate_optimal_paths_gpmp2.py:95-110, :156-159; generate_2d_dataset.py:225-226): an OMPL
+ * RRT* run of 4 seconds per problem (init_planner.plan(start_conf, goal_conf, 4.0)), interpolate(num_states) and path_to_traj_avg_vel (utils/planner_utils.py:60-71).
+ * RRT* is randomised and OMPL is not part of this build, so the PATH below has no counterpart in the reference and no fixture from it; what has one is the validity
+ * rule -- RRTStar.isStateValid -> Env2D.is_feasible(state, sphere_radius + epsilon_dist) (diff_gpmp2/ompl_rrtstar.py:18, :48-50) -- and the velocities of
+ * path_to_traj_avg_vel.  The rule stated here is exact: tests/paths_oracle.py restates it and the kernel is held against that bit for bit.  No shortcutting or
+ * smoothing (OMPL's simplifySolution), no any-angle paths.
+ * dof == 2 handles only; x_lims, y_lims, n = num_states and total_time_sec come from the handle.  sdf: row-major grids of the handle's io_dtype, shared
+ * (batch_stride 0) or one per sample, sides up to 2^12; DGP_SDF_TILED4 is refused with DGP_EINVAL (not implemented here: pass the row-major grid).  env_index as for
+ * dgp_sample_problems.  With res = (x_max - x_min) / W, orig_x = 0 - x_min / res, orig_y = 0 - y_min / res and the pixel coordinates px = orig_x + x / res,
+ * py = orig_y - y / res of the lookup:
+ * Cells.  The point of cell (r, c) is the world point whose pixel coordinates are exactly (c, r): x = (c - orig_x) * res, y = (orig_y - r) * res; the bilinear lookup
+ *   returns sdf[r][c] there.  The cell of a point: c = clamp(floor(px + 0.5), 0, W - 1), r = clamp(floor(py + 0.5), 0, H - 1).  A cell is free where its stored
+ *   distance, converted to double, is > clearance.
+ * Moves.  8 neighbours; an axis move costs 5, a diagonal move 7; a diagonal move is allowed only if both cells that share its corner are free (no corner cutting).
+ *   uint32 arithmetic, INF = 0xffffffff, INF + cost = INF.
+ * Distance field D (the goal's cost-to-go).  D = INF everywhere, D[goal cell] = 0 if that cell is free.  The CLOSURE of a row sets every free cell c to
+ *   min_k (D[r][k] + 5 |c - k|) over the cells k of its maximal run of free cells.  A DOWN PASS visits r = 0 .. H-1 in order: for r >= 1 each free cell takes the
+ *   minimum of itself and the allowed moves from row r-1 (final for this pass), then row r is closed (row 0 is only closed).  An UP PASS is the mirror image,
+ *   r = H-1 .. 0 from row r+1.  A SWEEP is a down pass followed by an up pass; the loop ends after the first sweep that changed no cell, or after max_sweeps sweeps.
+ *   A field that ended by the first condition is a fixed point of every edge relaxation: THE 5-7 shortest-path field, whatever order a kernel relaxes in.
+ *   `field` (B,H,W) holds D at return, blocked cells INF.
+ * Trace.  L cells are visited, starting at the start cell: while D[cur] > 0 (and fewer than H W cells were visited), step to the first neighbour, in the order
+ *   (dr, dc) = (0,+1), (-1,0), (0,-1), (+1,0), (-1,+1), (-1,-1), (+1,-1), (+1,+1), that is inside the grid, free, allowed as a diagonal move and has
+ *   D[nb] + cost == D[cur]; the trace ends where there is none.  path_cells (B, path_cap): r * W + c of the first path_cap cells, -1 behind them; num_cells (B): L.
+ * Trajectory.  Vertices V_0 = the start point itself, V_1 .. V_L the points of the traced cells, V_{L+1} = the goal point itself.  fp64, FMA contraction off:
+ *   l_j = sqrt(dx*dx + dy*dy) of segment j = V_j V_{j+1}, s_0 = 0, s_{j+1} = s_j + l_j summed serially, S = s_{L+1} -> length (B).  Row i (0 .. N = n - 1):
+ *   t = S * i / N (the product first); j the lowest index with s_{j+1} >= t (the last segment if there is none); f = l_j > 0 ? (t - s_j) / l_j : 0; position
+ *   V_j + f * (V_{j+1} - V_j).  Row N is the goal point itself, not interpolated; with S == 0 every row is the start point.  Velocities (goal - start) /
+ *   total_time_sec on every row (path_to_traj_avg_vel).  th_init (B,n,4) io_dtype, every value rounded once on store.
+ * info (B): bit 0 the start cell is not free; bit 1 the goal cell is not free; bit 2 D[start cell] = INF in a converged field (unreachable; set along with bit 0
+ *   or 1 where the field of such a problem converged); bit 3 max_sweeps sweeps were run and the last still changed a cell; bit 4 L > path_cap.  With any of bits
+ *   0-3 set th_init is the straight line of dgp_sample_problems (same formula and operation order), num_cells 0, path_cells all -1 and length the straight
+ *   distance sqrt(dx*dx + dy*dy); bit 4 only truncates path_cells.  Every output is always written.  A problem is a pure function of its grid, start, goal and
+ *   params: independent of batch size, position in the batch and launch shape.
+ * `field` is workspace AND output and is required; path_cells, num_cells, length and info may each be NULL.
+ * DGP_EINVAL, nothing launched: a NULL handle, params, sdf, start, goal, th_init or field; dof != 2; batch < 1; max_sweeps outside 1 .. 4096; path_cap < 0; a NaN
+ * clearance; a tiled grid; H or W beyond 2^12.
+ * One launch, no atomics, nothing allocated or synchronised: capturable in a HIP graph. */
+typedef struct DgpPathParams {
+  double  clearance;   /* a cell is free where its stored distance, converted to double, is > clearance; reference: sphere_radius + epsilon_dist (ompl_rrtstar.py:18) */
+  int32_t max_sweeps;  /* bound on the sweeps of the distance field, 1 .. 4096 */
+  int32_t path_cap;    /* second dimension of path_cells (>= 0) */
+} DgpPathParams;
+int dgp_init_paths(const DgpHandle* h, int32_t batch, const DgpSdf* sdf, const int32_t* env_index, const DgpPathParams* p,
+                   const void* start, const void* goal,            /* (B,1,4) io_dtype */
+                   void* th_init,                                  /* (B,n,4) io_dtype */
+                   uint32_t* field,                                /* (B,H,W): workspace AND output, required */
+                   int32_t* path_cells, int32_t* num_cells, double* length, int32_t* info,   /* each may be NULL */
+                   void* stream);
+
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
  * hipExtLaunchKernelGGL does -- hipEventElapsedTime(start, stop) is then that kernel's execution time, the quantity
