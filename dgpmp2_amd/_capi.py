@@ -26,6 +26,11 @@ DGP_OBST_MAX_BOXES, DGP_OBST_MAX_POINTS, DGP_OBST_MAX_GENERATORS = 64, 32, 4
 METRIC_NAMES = ('avg_vel', 'avg_acc', 'avg_jerk', 'gp_mse', 'in_coll', 'num_penetrating', 'avg_penetration', 'max_penetration', 'coll_intensity',
                 'constraint_violation', 'pos_mse', 'vel_mse', 'traj_mse')
 DGP_METRIC_COUNT = len(METRIC_NAMES)
+# columns of dgp_gp_interpolate's (B, DGP_DENSE_COUNT) float64 summary, in the header's order (DGP_DENSE_*)
+DENSE_NAMES = ('in_coll', 'num_colliding', 'avg_penetration', 'max_penetration', 'first_colliding', 'worst_index')
+DGP_DENSE_IN_COLL, DGP_DENSE_NUM_COLLIDING, DGP_DENSE_AVG_PENETRATION, DGP_DENSE_MAX_PENETRATION, DGP_DENSE_FIRST_COLLIDING, DGP_DENSE_WORST_INDEX = range(6)
+DGP_DENSE_COUNT = len(DENSE_NAMES)
+DGP_MAX_NUM_INTER = 1023
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DGP_LIB_PATH') or os.path.join(_HERE, 'lib', 'libdgpmp2_hip.so')   # override: tuning builds only
@@ -75,7 +80,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'gp_interpolate', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -143,6 +148,11 @@ class CApi(object):
     if self.init_paths is not None:
       self.init_paths.restype = C.c_int
       self.init_paths.argtypes = [vp, i32, C.POINTER(DgpSdf), vp, C.POINTER(DgpPathParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    # dgp_gp_interpolate: no twin in the emulator either
+    self.gp_interpolate = getattr(self.lib, prefix + 'gp_interpolate', None)
+    if self.gp_interpolate is not None:
+      self.gp_interpolate.restype = C.c_int
+      self.gp_interpolate.argtypes = [vp, i32, vp, i32, C.POINTER(DgpSdf), dbl, vp, vp, vp, vp]
     self.time_next_launch = f('time_next_launch'); self.time_next_launch.restype = C.c_int; self.time_next_launch.argtypes = [vp, vp]
     self.event_create = f('event_create'); self.event_create.restype = C.c_int; self.event_create.argtypes = [C.POINTER(vp)]
     self.event_destroy = f('event_destroy'); self.event_destroy.restype = None; self.event_destroy.argtypes = [vp]
@@ -201,7 +211,7 @@ import sysconfig
 # never loaded by mistake
 PYCALL_PATH = os.path.join(_HERE, 'lib', '_dgp_pycall' + (sysconfig.get_config_var('EXT_SUFFIX') or '.so'))
 _PYCALL_ENTRIES = ('gn_step', 'gn_solve', 'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward',
-                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'traj_metrics')
+                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'traj_metrics', 'gp_interpolate')
 
 
 def get_api():
@@ -250,6 +260,10 @@ class CtypesPycall(object):
   def traj_metrics(self, *a):
     # (handle, batch, th, the seven DgpSdf fields, metric_eps, th_opt, metrics, obs_error, stream)
     return self.api.traj_metrics(a[0], a[1], a[2], self._sdf(a, 3), *a[10:])
+
+  def gp_interpolate(self, *a):
+    # (handle, batch, th, num_inter, the seven DgpSdf fields, eps, th_dense, dense_cost, summary, stream)
+    return self.api.gp_interpolate(a[0], a[1], a[2], int(a[3]), self._sdf(a, 4), *a[11:])
 
 
 def get_pycall():
@@ -387,6 +401,13 @@ class Solver(object):
     if self.api.traj_metrics is None:
       raise NotImplementedError('%s does not export %straj_metrics (the CPU emulator has no twin of the metrics kernel)' % (self.api.path, self.api.prefix))
     self.api.check(self.api.traj_metrics(self.handle, batch, th, C.byref(sdf), float(metric_eps), th_opt, metrics, obs_error, stream))
+
+  def gp_interpolate(self, batch, th, num_inter, sdf=None, eps=0.0, th_dense=None, dense_cost=None, summary=None, stream=None):
+    """dgp_gp_interpolate: th_dense (B, N_d, d) and dense_cost (B, N_d) of the I/O type and / or summary (B, DGP_DENSE_COUNT) float64, N_d = (n - 1)(num_inter + 1) + 1,
+    one launch; sdf may be None when only th_dense is asked for."""
+    if self.api.gp_interpolate is None:
+      raise NotImplementedError('%s does not export %sgp_interpolate (the CPU emulator has no twin of the interpolation kernel)' % (self.api.path, self.api.prefix))
+    self.api.check(self.api.gp_interpolate(self.handle, batch, th, int(num_inter), C.byref(sdf) if sdf is not None else None, float(eps), th_dense, dense_cost, summary, stream))
 
   @staticmethod
   def sample_params(clearance, margin=0.5, min_dist_frac=0.6, near_tries=15, max_draws=4096, corner_inset=0.2):

@@ -35,6 +35,13 @@ inline int max_states(int dof) { return dof == 3 ? kMaxStatesLong6 : kMaxStatesL
 inline bool is_long(int n) { return n > kMaxStates; }
 inline bool shape_supported(int lpt, int c) { return (lpt == 16 || lpt == 32 || lpt == 64) && (c == 1 || c == 2 || c == 4); }
 
+// dgp_gp_interpolate (gp_interpolate.hip): at most kMaxNumInter interpolated states per interval; N_d = (n - 1)(K + 1) + 1 dense states (at most 1023 * 1024 + 1);
+// lanes per trajectory from N_d -- the lanes walk the DENSE index -- at the thresholds of the metrics kernel: every lane has up to four dense states before a
+// wider group pays (one round of memory latency either way, traj_metrics.hip).
+constexpr int kMaxNumInter = 1023;
+inline int dense_states(int n, int num_inter) { return (n - 1) * (num_inter + 1) + 1; }
+inline int dense_lpt(int nd) { return nd <= 64 ? 16 : (nd <= 128 ? 32 : 64); }
+
 // Pick (LPT, C) for n states and a batch of B trajectories: the cheapest supported shape under a two-parameter timing model
 // fitted to profiles/tools/shape_grid.py on MI355X (static-covariance kernels, steady clocks):
 //   time(shape, B) ~ fixed + T[shape] * max(1, 1.25 * wavefronts / 1024)

@@ -40,6 +40,8 @@ typedef int (*square_covs_fn)(const void*, int32_t, int32_t, int32_t, int32_t, i
 typedef int (*square_covs_bwd_fn)(const void*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, const void*, const void*, const void*, void*, void*);
 typedef int (*traj_metrics_fn)(const DgpHandle*, int32_t, const void*, const DgpSdf*, double, const void*, double*, void*, void*);
 static traj_metrics_fn f_traj_metrics;
+typedef int (*gp_interpolate_fn)(const DgpHandle*, int32_t, const void*, int32_t, const DgpSdf*, double, void*, void*, double*, void*);
+static gp_interpolate_fn f_gp_interpolate;
 static square_covs_fn f_square_covs;
 static square_covs_bwd_fn f_square_covs_bwd;
 typedef int (*sum_partial_grids_fn)(const void*, int32_t, int32_t, int64_t, double, void*, int32_t, void*);
@@ -89,7 +91,7 @@ static inline int64_t as_i64(PyObject* o, int* bad) {
   const DgpSdf* sdfp = sdf.data ? &sdf : NULL
 
 static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
-  NEED(13, "bind");
+  NEED(14, "bind");
   f_gn_step = (gn_step_fn)P(0);
   f_gn_solve = (gn_solve_fn)P(1);
   f_eval_errors = (eval_errors_fn)P(2);
@@ -103,6 +105,7 @@ static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
   f_square_covs = (square_covs_fn)P(10);
   f_square_covs_bwd = (square_covs_bwd_fn)P(11);
   f_traj_metrics = (traj_metrics_fn)P(12);
+  f_gp_interpolate = (gp_interpolate_fn)P(13);
   if (bad) return NULL;
   Py_RETURN_NONE;
 }
@@ -288,9 +291,25 @@ static PyObject* py_traj_metrics(PyObject* self, PyObject* const* a, Py_ssize_t 
   return PyLong_FromLong(f_traj_metrics(h, batch, th, sdf.data ? &sdf : NULL, eps, th_opt, (double*)metrics, obs_error, stream));
 }
 
+/* gp_interpolate(handle, batch, th, num_inter, sdf_data, sdf_rows, sdf_cols, sdf_batch_stride, sdf_layout, sdf_grad_mode, sdf_grad_indices, eps, th_dense, dense_cost, summary, stream) */
+static PyObject* py_gp_interpolate(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
+  NEED(16, "gp_interpolate");
+  BOUND(f_gp_interpolate);
+  const DgpHandle* h = (const DgpHandle*)P(0);
+  const int32_t batch = (int32_t)I(1);
+  const void* th = P(2);
+  const int32_t num_inter = (int32_t)I(3);
+  DgpSdf sdf = {P(4), (int32_t)I(5), (int32_t)I(6), I(7), (int32_t)I(8), (int32_t)I(9), (int64_t*)P(10)};
+  const double eps = PyFloat_AsDouble(a[11]);
+  if (eps == -1.0 && PyErr_Occurred()) return NULL;
+  void *th_dense = P(12), *dense_cost = P(13), *summary = P(14), *stream = P(15);
+  if (bad) return NULL;
+  return PyLong_FromLong(f_gp_interpolate(h, batch, th, num_inter, sdf.data ? &sdf : NULL, eps, th_dense, dense_cost, (double*)summary, stream));
+}
+
 static PyMethodDef methods[] = {
     {"bind", (PyCFunction)(void (*)(void))py_bind, METH_FASTCALL,
-     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward, traj_metrics): "
+     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward, traj_metrics, gp_interpolate): "
      "addresses of the C-ABI entry points"},
     {"gn_solve_traced", (PyCFunction)(void (*)(void))py_gn_solve_traced, METH_FASTCALL, "dgp_gn_solve_traced"},
     {"gn_solve_backward", (PyCFunction)(void (*)(void))py_gn_solve_backward, METH_FASTCALL, "dgp_gn_solve_backward"},
@@ -300,6 +319,7 @@ static PyMethodDef methods[] = {
     {"square_covariances", (PyCFunction)(void (*)(void))py_square_covs, METH_FASTCALL, "dgp_square_covariances"},
     {"square_covariances_backward", (PyCFunction)(void (*)(void))py_square_covs_bwd, METH_FASTCALL, "dgp_square_covariances_backward"},
     {"traj_metrics", (PyCFunction)(void (*)(void))py_traj_metrics, METH_FASTCALL, "dgp_traj_metrics"},
+    {"gp_interpolate", (PyCFunction)(void (*)(void))py_gp_interpolate, METH_FASTCALL, "dgp_gp_interpolate"},
     {"gn_step", (PyCFunction)(void (*)(void))py_gn_step, METH_FASTCALL, "dgp_gn_step"},
     {"gn_solve", (PyCFunction)(void (*)(void))py_gn_solve, METH_FASTCALL, "dgp_gn_solve"},
     {"eval_errors", (PyCFunction)(void (*)(void))py_eval_errors, METH_FASTCALL, "dgp_eval_errors"},

@@ -1,0 +1,194 @@
+// gp_interpolate.hip -- dgp_gp_interpolate: the GP-interpolated dense trajectory of every trajectory of a batch, the hinge cost of every dense state and a
+// collision summary over them, in ONE launch (gfx950 / CDNA4).
+//
+// What it builds: the capability the reference names and never implements -- gpmp2_planner.py:29-41 reads planner_params['total_check_step'] / ['use_gp_inter'], derives
+// check_inter and sizes num_obs_factors for it, examples/gpmp2_xyh_params.yaml:7-8 carries the keys, and no code interpolates anything.  The rule is GPMP2's: the posterior
+// mean of the constant-velocity prior between two support states, Lambda(tau) theta_i + Psi(tau) theta_{i+1} with Phi, Q, Q^-1 of gp/gp_factor.py:31-53; Q_c cancels, so
+// one rule serves every covariance mode.  include/dgpmp2_hip.h states the closed form and its operation order, tests/interp_oracle.py restates it, and the kernel is held
+// against that bit for bit.
+//
+// Mapping: LPT = 16 / 32 / 64 lanes per trajectory, chosen from the number of DENSE states N_d = (n - 1)(K + 1) + 1 (dgp_host::dense_lpt), 64 / LPT trajectories per
+// wavefront.  The lanes of a trajectory walk the dense index in a strided loop, m = lane + k LPT: adjacent lanes store adjacent rows of th_dense and adjacent entries of
+// dense_cost (coalesced runs) and read the same or neighbouring support rows i = m / (K + 1), i + 1 -- the lines are in flight or in the vector L1 already, as for the
+// neighbour rows of traj_metrics.hip.  Row i + 1 is clamped to n - 1 for the load (unconditional loads); the copy rule (offset 0 is a bit copy of row i) leaves the
+// clamped row unused.  The obstacle lookup is gn_lane.h's obstacle_eval at the UNROUNDED fp64 position: a dense state has a hinge cost exactly where a support state at
+// that position would in the step and metrics kernels.  DGP_TL = 2 (this unit's flag): the grid layout is a run-time branch, one kernel for both layouts.
+// Reduction: every lane keeps an fp64 partial sum, a maximum with its index, a count and a minimum first index of its dense states, then a butterfly over the
+// trajectory's LPT lanes -- a fixed order that depends on N_d and LPT only: no atomics, no LDS, bit-identical results from run to run, for either grid layout and
+// wherever the trajectory sits in the batch.  Lanes 0 .. 5 of a trajectory store its DGP_DENSE_COUNT doubles as one contiguous run.  Lane groups past the end of a
+// ragged batch recompute the last trajectory and store nothing (no divergent shuffles).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#ifndef DGP_TL
+#define DGP_TL 2
+#endif
+#include "dgp_host.h"
+#include "dgp_launch.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using dgp_host::fail;
+
+struct InterpArgs {
+  dgp::GnParams p;         // B, n, th, the grid and the constants of the bilinear lookup (dgp_host::fill_call); dt
+  void* th_dense;          // (B, N_d, d) or null
+  void* dense_cost;        // (B, N_d) or null
+  double* summary;         // (B, DGP_DENSE_COUNT) or null
+  double eps;
+  int32_t k1;              // num_inter + 1: dense states per interval
+  int32_t nd;              // N_d
+};
+static_assert(sizeof(InterpArgs) <= 4096, "kernel-argument segment");
+
+constexpr int NO_INDEX = 0x7fffffff;
+
+template <int LPT>
+__device__ __forceinline__ double group_sum(double v) {
+#pragma unroll
+  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
+  return v;
+}
+template <int LPT>
+__device__ __forceinline__ int group_sum_i(int v) {
+#pragma unroll
+  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
+  return v;
+}
+template <int LPT>
+__device__ __forceinline__ int group_min_i(int v) {
+#pragma unroll
+  for (int m = 1; m < LPT; m <<= 1) {
+    const int o = __shfl_xor(v, m);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+// the maximum with its index: a NaN wins over every number (torch.max), the smaller index wins between equals (and between NaNs).
+// Symmetric: both partners of an exchange end with the same pair.
+template <int LPT>
+__device__ __forceinline__ void group_argmax(double& v, int& idx) {
+#pragma unroll
+  for (int m = 1; m < LPT; m <<= 1) {
+    const double ov = __shfl_xor(v, m);
+    const int oi = __shfl_xor(idx, m);
+    const bool vn = v != v, on = ov != ov;
+    const bool greater = (on && !vn) || ov > v, equal = (on && vn) || ov == v;
+    const bool take = greater || (equal && oi < idx);
+    v = take ? ov : v;
+    idx = take ? oi : idx;
+  }
+}
+
+template <int DOF, typename IO, int LPT>
+__global__ void __launch_bounds__(64) gp_interpolate_kernel(const InterpArgs a) {
+  constexpr int D = 2 * DOF, TPW = 64 / LPT;
+  const dgp::GnParams& p = a.p;
+  const int lane = (int)threadIdx.x, l = lane % LPT;
+  const int64_t b_raw = (int64_t)blockIdx.x * TPW + lane / LPT;
+  const bool on = b_raw < p.B;
+  const int64_t b = on ? b_raw : (int64_t)p.B - 1;
+  const int n = p.n, k1 = a.k1, nd = a.nd;
+  const IO* th = (const IO*)p.th + b * n * D;
+  const IO* grid = (const IO*)p.sdf + b * p.sdf_bstride;      // (null without a cost / summary output: not read then)
+  IO* dense = (IO*)a.th_dense + b * nd * D;
+  IO* ocost = (IO*)a.dense_cost + b * nd;
+  const bool look = a.dense_cost != nullptr || a.summary != nullptr;      // wave-uniform
+  const double dt = p.dt, fk1 = (double)k1;
+  double s_pen = 0.0, m_pen = -__builtin_huge_val();
+  int m_idx = NO_INDEX, cnt = 0, first = NO_INDEX;
+  for (int m = l; m < nd; m += LPT) {
+    const int i = m / k1, j = m - i * k1;
+    const int i1 = i + 1 < n ? i + 1 : n - 1;      // clamped: the last dense state is a copy (j == 0), the row is unused
+    IO r0[D], r1[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) { r0[c] = th[(int64_t)i * D + c]; r1[c] = th[(int64_t)i1 * D + c]; }
+    // the eight coefficients, in the header's operation order
+    const double s = (double)j / fk1;
+    const double s2 = s * s;
+    const double s3 = s2 * s;
+    const double a0 = (1.0 - 3.0 * s2) + 2.0 * s3;
+    const double a1 = dt * ((s - 2.0 * s2) + s3);
+    const double a2 = 3.0 * s2 - 2.0 * s3;
+    const double a3 = dt * (s3 - s2);
+    const double b2 = (6.0 * (s - s2)) / dt;
+    const double b0 = -b2;
+    const double b1 = (1.0 - 4.0 * s) + 3.0 * s2;
+    const double b3 = 3.0 * s2 - 2.0 * s;
+    const bool copy = j == 0;
+    double q[D];
+#pragma unroll
+    for (int c = 0; c < DOF; ++c) {
+      const double x0 = (double)r0[c], v0 = (double)r0[DOF + c], x1 = (double)r1[c], v1 = (double)r1[DOF + c];
+      q[c] = ((a0 * x0 + a1 * v0) + a2 * x1) + a3 * v1;
+      q[DOF + c] = ((b0 * x0 + b1 * v0) + b2 * x1) + b3 * v1;
+    }
+    if (a.th_dense != nullptr && on) {
+#pragma unroll
+      for (int c = 0; c < D; ++c) dense[(int64_t)m * D + c] = copy ? r0[c] : (IO)q[c];      // a support state passes through untouched, bit for bit
+    }
+    if (look) {
+      double cost, hx, hy;
+      dgp::obstacle_eval<IO>(p, grid, copy ? (double)r0[0] : q[0], copy ? (double)r0[1] : q[1], a.eps, cost, hx, hy);
+      if (a.dense_cost != nullptr && on) ocost[m] = (IO)cost;
+      const bool interior = m >= 1 && m < nd - 1;      // collision_metrics' convention: the first and the last state are left out
+      s_pen += interior ? cost : 0.0;
+      const bool hit = interior && cost != 0.0;        // torch.nonzero: a NaN counts
+      cnt += hit ? 1 : 0;
+      first = (hit && m < first) ? m : first;
+      const bool take = interior && ((cost != cost && !(m_pen != m_pen)) || cost > m_pen);      // m rises: the smallest index of equals stays
+      m_pen = take ? cost : m_pen;
+      m_idx = take ? m : m_idx;
+    }
+  }
+  if (a.summary == nullptr) return;
+  s_pen = group_sum<LPT>(s_pen);
+  group_argmax<LPT>(m_pen, m_idx);
+  cnt = group_sum_i<LPT>(cnt);
+  first = group_min_i<LPT>(first);
+  double out;
+  switch (l) {
+    case DGP_DENSE_IN_COLL: out = cnt > 0 ? 1.0 : 0.0; break;
+    case DGP_DENSE_NUM_COLLIDING: out = (double)cnt; break;
+    case DGP_DENSE_AVG_PENETRATION: out = s_pen / (double)(nd - 2); break;
+    case DGP_DENSE_MAX_PENETRATION: out = m_pen; break;
+    case DGP_DENSE_FIRST_COLLIDING: out = first == NO_INDEX ? -1.0 : (double)first; break;
+    case DGP_DENSE_WORST_INDEX: out = (double)m_idx; break;
+    default: out = 0.0; break;
+  }
+  if (on && l < DGP_DENSE_COUNT) a.summary[b * DGP_DENSE_COUNT + l] = out;
+}
+
+template <int DOF, typename IO>
+hipError_t launch_lpt(int lpt, const InterpArgs& a, hipStream_t s, const dgp_dev::Events& ev) {
+  const int tpw = 64 / lpt;
+  const dim3 grid((unsigned)((a.p.B + tpw - 1) / tpw)), block(64);
+  if (lpt == 16) return dgp_dev::launch(gp_interpolate_kernel<DOF, IO, 16>, grid, block, 0, s, ev, a);
+  if (lpt == 32) return dgp_dev::launch(gp_interpolate_kernel<DOF, IO, 32>, grid, block, 0, s, ev, a);
+  return dgp_dev::launch(gp_interpolate_kernel<DOF, IO, 64>, grid, block, 0, s, ev, a);
+}
+
+}  // namespace
+
+extern "C" int dgp_gp_interpolate(const DgpHandle* h, int32_t batch, const void* th, int32_t num_inter, const DgpSdf* sdf, double eps,
+                                  void* th_dense, void* dense_cost, double* summary, void* stream) {
+  const dgp_dev::Events ev = dgp_dev::take_events();
+  InterpArgs a;
+  const int rc = dgp_host::fill_call(h, batch, th, /*start=*/th, /*goal=*/th, sdf, nullptr, a.p, /*sdf_optional=*/true);      // (no start / goal here: th stands in for the null checks)
+  if (rc != DGP_OK) return rc;
+  if (!th_dense && !dense_cost && !summary) return fail(DGP_EINVAL, "dgp_gp_interpolate: th_dense, dense_cost and summary are all null");
+  if ((dense_cost || summary) && (!sdf || !sdf->data)) return fail(DGP_EINVAL, "dgp_gp_interpolate: dense_cost and summary need the signed-distance grid (sdf)");
+  if (num_inter < 0 || num_inter > dgp_host::kMaxNumInter)
+    return fail(DGP_EINVAL, "dgp_gp_interpolate: num_inter must be in 0..%d, got %d", dgp_host::kMaxNumInter, num_inter);
+  a.k1 = num_inter + 1;
+  a.nd = dgp_host::dense_states(a.p.n, num_inter);
+  if (summary && a.nd < 3) return fail(DGP_EINVAL, "dgp_gp_interpolate: the summary needs at least 3 dense states (no interior state), got %d", a.nd);
+  a.th_dense = th_dense; a.dense_cost = dense_cost; a.summary = summary; a.eps = eps;
+  const int lpt = dgp_host::dense_lpt(a.nd);
+  hipStream_t s = (hipStream_t)stream;
+  const bool f64 = h->cfg.io_dtype == DGP_F64;
+  const hipError_t e = h->cfg.dof == 2 ? (f64 ? launch_lpt<2, double>(lpt, a, s, ev) : launch_lpt<2, float>(lpt, a, s, ev))
+                                       : (f64 ? launch_lpt<3, double>(lpt, a, s, ev) : launch_lpt<3, float>(lpt, a, s, ev));
+  return dgp_dev::hip_rc(e, "dgp_gp_interpolate");
+}

@@ -145,7 +145,7 @@ def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, c
 
 
 def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, first_diagonal=True, require_collision_free=True, dataset_type=None, num_envs=None,
-                     im_size=None, obstacle_params=None, init='straight', **params):
+                     im_size=None, obstacle_params=None, init='straight', check_inter=0, **params):
   """The reference's generation chain for a batch of environments, on the device until the files are written:
     0. images=None: generate_obstacle_maps(planner, dataset_type, num_envs, im_size, seed=seed, **obstacle_params) makes the images (uint8); an environment whose
        map is flagged capped or overlapping is dropped before anything else runs           (generate_2d_dataset.py:194-208; the reference never returns such a map)
@@ -155,6 +155,9 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
     3. planner.forward on the initial trajectories: the straight lines (init='straight'), or init_paths' collision-free grid paths (init='grid_path': the
        reference's --rrt_star_init switch, :95-110, :156-159; generate_2d_dataset.py:225-226)                                                   (:181-184)
     4. trajectory_metrics(eps=0): in_coll of every planned trajectory             (generate_2d_dataset.py:247-252)
+       check_inter > 0: the verdict is that of the GP-interpolated dense trajectory with check_inter states inside every interval, planner.interpolate(th_opt,
+       check_inter, sdfb, eps=0).in_collision -- a trajectory whose support states straddle an obstacle is caught (the reference's 'total_check_step' /
+       'use_gp_inter' keys, gpmp2_planner.py:29-41, name this check and nothing implements it); 0, the default: the support states only, as the reference
     5. write_environment / write_problem / write_meta
   images: (E,H,W) or (E,1,H,W) device tensor, free space > 0.75.  An environment with a problem whose sampling hit max_draws is dropped; so is one with a planned
   trajectory in collision when require_collision_free is set (the reference drops an environment by exception, :247-265).  Written environments are numbered densely.
@@ -175,7 +178,7 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
     r = {'num_envs': 0, 'kept': [], 'dropped': {}, 'path_info': None}
     if good:
       r = generate_dataset(root_dir, mode, gen[sel], planner, probs_per_env, seed=seed, first_diagonal=first_diagonal,
-                           require_collision_free=require_collision_free, init=init, **params)
+                           require_collision_free=require_collision_free, init=init, check_inter=check_inter, **params)
     else:
       write_meta(root_dir, mode, 0, int(probs_per_env), {'x_lims': [float(v) for v in planner.env_params['x_lims']], 'y_lims': [float(v) for v in planner.env_params['y_lims']]},
                  int(gen.shape[-1]))
@@ -206,7 +209,8 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
   imb = (im > 0.75).to(sdf.dtype).unsqueeze(1).index_select(0, env_index.long())
   with torch.no_grad():
     th_opt = planner.forward(th_initb, startb, goalb, imb, sdfb)[0]
-    in_coll = planner.trajectory_metrics(th_opt, sdfb, eps=0.0).in_collision
+    if int(check_inter) > 0: in_coll = planner.interpolate(th_opt, int(check_inter), sdfb, eps=0.0).in_collision
+    else: in_coll = planner.trajectory_metrics(th_opt, sdfb, eps=0.0).in_collision
   capped_h, coll_h = info.capped.view(E, P).any(1).cpu().numpy(), in_coll.view(E, P).any(1).cpu().numpy()
   s_h, g_h, th_h = startb.cpu().numpy(), goalb.cpu().numpy(), th_opt.cpu().numpy()
   im_h, sdf_h = (im > 0.75).to(torch.float64).cpu().numpy(), sdf[:, 0].cpu().numpy()

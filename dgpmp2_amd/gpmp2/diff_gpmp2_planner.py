@@ -490,6 +490,14 @@ class DiffGPMP2Planner(nn.Module):
     metrics obstacle factor (the reference uses 0.0).  No autograd; usable inside graphed_iteration / torch.cuda.graph."""
     return self.plan_layer.trajectory_metrics(thb, sdfb, th_optb, eps, return_obs_error)
 
+  def interpolate(self, thb, num_inter, sdfb=None, eps=0.0, return_cost=False):
+    """GPMP2's GP interpolation of every trajectory of the batch -- num_inter states inside every interval -- and, with sdfb, the collision check of every dense
+    state, in one launch: -> plan_layer.DenseTrajectory with `.th` (B, N_d, d), `.times` (N_d,) and, with grids, the (B,) device tensors in_collision (bool),
+    num_colliding, first_colliding, worst_index (int), avg_penetration, max_penetration, `.raw` (B, 6) float64 and `.cost` (B, N_d) when asked for.  The
+    capability the reference's 'total_check_step' / 'use_gp_inter' keys name (gpmp2_planner.py:29-41).  No autograd; usable inside graphed_iteration /
+    torch.cuda.graph."""
+    return self.plan_layer.interpolate(thb, num_inter, sdfb, eps, return_cost)
+
   def get_covariances(self, out, mode='diag_identity', learn_eps=False):
     """Learn-module output (B,1,out_dim) -> covariance tensors (diff_gpmp2_planner.py:247-290).
     fix_dynamics: obscov[, eps];  diag_identity: q^2 I;  qc_full: q q^T (dof);  q_full: q q^T (state_dim);  'diag' raises."""

@@ -1078,6 +1078,34 @@ class PlanLayer(nn.Module):
     _launch(dev, self._pc.traj_metrics, solver.h, B, thc.data_ptr(), *sd[:7], float(eps), _ptr(opt), raw.data_ptr(), _ptr(oerr), _raw_stream(dev))
     return TrajectoryMetrics(raw, oerr)
 
+  def interpolate(self, thb, num_inter, sdfb=None, eps=0.0, return_cost=False):
+    """The GP-interpolated dense trajectory of every trajectory of the batch -- num_inter states inside every interval, N_d = (n - 1)(num_inter + 1) + 1 in all --
+    and, with sdfb, the collision check of every dense state, in ONE launch (dgp_gp_interpolate; include/dgpmp2_hip.h states the rule, utils.planner_utils.
+    gp_interpolate_traj is its torch mirror).  The reference names the capability (gpmp2_planner.py:29-41: 'total_check_step', 'use_gp_inter') and never builds it.
+    thb (B,n,d); sdfb as for trajectory_metrics (row-major, TiledSdf, expand()ed shared grids) or None: interpolation only; eps the epsilon of the check (a dense
+    state collides where dist <= eps + sphere_radius).  No autograd: inputs are detached.  -> DenseTrajectory."""
+    if thb.dim() != 3 or thb.shape[1] != self.num_traj_states or thb.shape[2] != self.state_dim:
+      raise ValueError('thb must be (B,%d,%d), got %s' % (self.num_traj_states, self.state_dim, tuple(thb.shape)))
+    K = int(num_inter)
+    if K != num_inter or K < 0 or K > _capi.DGP_MAX_NUM_INTER: raise ValueError('num_inter must be an integer in 0..%d, got %r' % (_capi.DGP_MAX_NUM_INTER, num_inter))
+    if return_cost and sdfb is None: raise ValueError('interpolate(return_cost=True) needs the signed-distance grids (sdfb)')
+    B, dtype = thb.shape[0], thb.dtype
+    solver = self._solvers.get(dtype) or self._solver(dtype)
+    dev = thb.get_device()
+    if dev < 0: _require_cuda(thb, 'thb')
+    nd = (self.num_traj_states - 1) * (K + 1) + 1
+    if sdfb is not None and nd < 3: raise ValueError('the collision summary needs at least 3 dense states, got %d' % nd)
+    if sdfb is not None and self.auto_tile: sdfb = self._auto_tiled(sdfb, B)
+    sd = self._sdf_args(sdfb, dtype, B, dev)
+    thc = thb.detach().contiguous()
+    dense = torch.empty((B, nd, self.state_dim), dtype=dtype, device=thc.device)
+    raw = torch.empty((B, _capi.DGP_DENSE_COUNT), dtype=torch.float64, device=thc.device) if sdfb is not None else None
+    cost = torch.empty((B, nd), dtype=dtype, device=thc.device) if return_cost else None
+    _launch(dev, self._pc.gp_interpolate, solver.h, B, thc.data_ptr(), K, *sd[:7], float(eps), dense.data_ptr(), _ptr(cost), _ptr(raw), _raw_stream(dev))
+    from ..utils.planner_utils import gp_interpolate_times
+    times = gp_interpolate_times(_f(self.total_time_sec), self.total_time_step, K, dtype=torch.float64, device=thc.device)
+    return DenseTrajectory(dense, times, raw, cost)
+
   def sample_problems(self, sdfb, num_problems, params, dtype=torch.float64, env_index=None, diagonal=None, seed=0, first_problem=0):
     """Feasible start / goal pairs and their straight-line initial trajectories in ONE launch (dgp_sample_problems; datasets.problem_generation.sample_problems is the
     documented front end and fills `params`, a _capi.DgpSampleParams).  sdfb as for forward() (row-major, TiledSdf, a shared grid); env_index (B) int32 device tensor:
@@ -1192,4 +1220,36 @@ class TrajectoryMetrics(object):
     return {k: getattr(self, k) for k in self.keys()}
 
 
-_NO_SDF = (None, 2, 2, 0, 0, 0, None, None)       # the seven fields of DgpSdf + the keep-alive slot
+class DenseTrajectory(object):
+  """Result of PlanLayer.interpolate: `th` the (B, N_d, d) dense trajectories, `times` the (N_d,) float64 query times, `raw` the (B, DGP_DENSE_COUNT) float64
+  device tensor dgp_gp_interpolate wrote (columns _capi.DENSE_NAMES; None without grids), `cost` the (B, N_d) raw hinge costs or None.  With grids, (B,) device tensors
+  over the dense states 1 .. N_d - 2: in_collision (bool), num_colliding, first_colliding (-1: none), worst_index (int64) -- formed on access by one small torch op
+  each -- and avg_penetration, max_penetration (views of `raw`)."""
+  __slots__ = ('th', 'times', 'raw', 'cost')
+  _COL = {name: i for i, name in enumerate(_capi.DENSE_NAMES)}
+  _INT = ('num_colliding', 'first_colliding', 'worst_index')
+
+  def __init__(self, th, times, raw=None, cost=None):
+    self.th, self.times, self.raw, self.cost = th, times, raw, cost
+
+  def __getattr__(self, name):
+    if name in DenseTrajectory.__slots__: raise AttributeError(name)
+    i = self._COL.get('in_coll' if name == 'in_collision' else name)
+    if i is None or name == 'in_coll': raise AttributeError(name)
+    if self.raw is None: raise AttributeError('%s: interpolate() was called without grids (sdfb)' % name)
+    if name == 'in_collision': return self.raw[:, i] != 0
+    if name in self._INT: return self.raw[:, i].to(torch.int64)
+    return self.raw[:, i]
+
+  def keys(self):
+    return ('in_collision', 'num_colliding', 'avg_penetration', 'max_penetration', 'first_colliding', 'worst_index') if self.raw is not None else ()
+
+  def __getitem__(self, name):
+    try: return getattr(self, name)
+    except AttributeError: raise KeyError(name)
+
+  def as_dict(self):
+    return {k: getattr(self, k) for k in self.keys()}
+
+
+_NO_SDF = (None, 2, 2, 0, 0, 0, None, None)      # the seven fields of DgpSdf + the keep-alive slot

@@ -83,3 +83,35 @@ def collision_metrics(traj, obs_error, total_time_sec, total_time_step):
   num_penetrating = torch.nonzero(interior).numel() / 2
   step_sec = total_time_sec * 1.0 / total_time_step * 1.0
   return num_penetrating > 0, interior.mean(), interior.max(), (num_penetrating * step_sec) / total_time_sec * 1.0
+
+
+def gp_interpolate_times(total_time_sec, total_time_step, num_inter, dtype=torch.float64, device=None):
+  """(N_d,) query times of the dense trajectory: dense index m = i (K + 1) + j lies at i dt + j dt / (K + 1), dt = total_time_sec / total_time_step."""
+  K1 = int(num_inter) + 1
+  dt = total_time_sec * 1.0 / total_time_step * 1.0
+  m = torch.arange(int(total_time_step) * K1 + 1, device=device)
+  return (m // K1).to(dtype) * dt + (m % K1).to(dtype) * dt / K1
+
+
+def gp_interpolate_traj(trajb, total_time_sec, total_time_step, num_inter):
+  """(B, n, d) support states -> (B, N_d, d) dense trajectory, N_d = (n - 1)(num_inter + 1) + 1: GPMP2's GP interpolation, the posterior mean of the
+  constant-velocity prior between two support states (Lambda(tau) theta_i + Psi(tau) theta_{i+1}; Q_c cancels).  The documented mirror of dgp_gp_interpolate
+  (include/dgpmp2_hip.h states the closed form) as plain batched torch ops on any device, in trajb's dtype: the reference reads the keys 'total_check_step' /
+  'use_gp_inter' (gpmp2_planner.py:29-41) and never interpolates.  Offset-0 rows are the support states themselves; the heading of the dof 3 robot is
+  interpolated like any other column.  DiffGPMP2Planner.interpolate does the same (in fp64, with the collision check of every dense state) in one launch."""
+  B, n, d = trajb.shape
+  if n != int(total_time_step) + 1: raise ValueError('trajb has %d states for total_time_step %d' % (n, total_time_step))
+  dof, K1 = d // 2, int(num_inter) + 1
+  if K1 < 1: raise ValueError('num_inter must be >= 0')
+  dt = total_time_sec * 1.0 / total_time_step * 1.0
+  if K1 == 1: return trajb.clone()
+  s = (torch.arange(K1, device=trajb.device, dtype=trajb.dtype) / K1).view(1, 1, K1, 1)
+  s2 = s * s
+  s3 = s2 * s
+  x0, v0, x1, v1 = (t.unsqueeze(2) for t in (trajb[:, :-1, :dof], trajb[:, :-1, dof:], trajb[:, 1:, :dof], trajb[:, 1:, dof:]))
+  pos = (((1.0 - 3.0 * s2) + 2.0 * s3) * x0 + (dt * ((s - 2.0 * s2) + s3)) * v0 + (3.0 * s2 - 2.0 * s3) * x1) + (dt * (s3 - s2)) * v1
+  b2 = (6.0 * (s - s2)) / dt
+  vel = ((-b2) * x0 + ((1.0 - 4.0 * s) + 3.0 * s2) * v0 + b2 * x1) + (3.0 * s2 - 2.0 * s) * v1
+  out = torch.cat((pos, vel), dim=-1)                       # (B, n - 1, K1, d)
+  out[:, :, 0] = trajb[:, :-1]                              # offset 0: the support state itself, no arithmetic
+  return torch.cat((out.reshape(B, (n - 1) * K1, d), trajb[:, -1:]), dim=1)

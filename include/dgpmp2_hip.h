@@ -492,6 +492,49 @@ int dgp_init_paths(const DgpHandle* h, int32_t batch, const DgpSdf* sdf, const i
                    int32_t* path_cells, int32_t* num_cells, double* length, int32_t* info,   /* each may be NULL */
                    void* stream);
 
+/* GP-interpolated dense trajectories and the collision check BETWEEN support states, ONE launch.  The reference names the capability and never builds it:
+ * gpmp2_planner.py:29-41 reads planner_params['total_check_step'] / ['use_gp_inter'], derives check_inter and sizes num_obs_factors for it, and no code interpolates.
+ * The rule is GPMP2's GP interpolation: the posterior mean of the constant-velocity prior at time tau inside an interval, Lambda(tau) theta_i + Psi(tau) theta_{i+1},
+ *   Psi = Q_tau Phi(Delta - tau)^T Q_Delta^-1,  Lambda = Phi(tau) - Psi Phi(Delta),  Phi, Q, Q^-1 those of gp/gp_factor.py:31-53.
+ * Q_c cancels: the rule holds for every covariance mode, the learned ones included.  The heading column of the dof 3 robot is interpolated like any other column (the
+ * reference's GP factor does no angle wrapping either).
+ * Symbols.  Delta = total_time_sec / (n - 1) (the handle's dt); K = num_inter >= 0 interpolated states per interval; the dense trajectory has N_d = (n - 1)(K + 1) + 1
+ *   states; dense index m belongs to interval i = m / (K + 1) at offset j = m % (K + 1), time i Delta + j Delta / (K + 1).
+ * Copies.  j == 0 is a copy of support state i (the last dense state, i = n - 1, included): bit for bit, NaN and -0.0 included, no arithmetic touches it.
+ * j >= 1.  fp64 whatever io_dtype, FMA contraction off, every operation in the order written, left to right inside a pair of parentheses:
+ *   s  = (double)j / (double)(K + 1),  s2 = s * s,  s3 = s2 * s
+ *   a0 = (1 - 3 s2) + 2 s3          a1 = Delta * ((s - 2 s2) + s3)      a2 = 3 s2 - 2 s3      a3 = Delta * (s3 - s2)
+ *   b2 = (6 * (s - s2)) / Delta     b0 = -b2                            b1 = (1 - 4 s) + 3 s2  b3 = 3 s2 - 2 s
+ *   and per dof component, x0, v0 columns c, dof + c of state i and x1, v1 those of state i + 1 (converted to double):
+ *   pos = ((a0 x0 + a1 v0) + a2 x1) + a3 v1          vel = ((b0 x0 + b1 v0) + b2 x1) + b3 v1
+ *   i.e. pos = (1 - 3s^2 + 2s^3) x0 + Delta (s - 2s^2 + s^3) v0 + (3s^2 - 2s^3) x1 + Delta (s^3 - s^2) v1,
+ *        vel = -6 (s - s^2) / Delta x0 + (1 - 4s + 3s^2) v0 + 6 (s - s^2) / Delta x1 + (3s^2 - 2s) v1.
+ *   Stored values are rounded once to io_dtype.
+ * Obstacle lookup.  Every dense state is looked up at its first two columns by the function of the step and metrics kernels (obstacle_cost.py:29-38), with eps given per
+ *   call: a hinge cost where dist <= eps + sphere_radius, exactly where a support state at that position has one.  For DGP_F32 the lookup takes the UNROUNDED fp64
+ *   interpolated position (a copied state: its stored value).
+ * th (B,n,d) io_dtype.  sdf as for dgp_traj_metrics (row-major or DGP_SDF_TILED4, shared or one grid per sample); may be NULL when dense_cost and summary are both NULL.
+ * Outputs (each may be NULL, not all three):
+ *   th_dense   (B, N_d, d) io_dtype
+ *   dense_cost (B, N_d) io_dtype: the raw hinge cost of every dense state; at K = 0 it is obs_error of dgp_traj_metrics
+ *   summary    (B, DGP_DENSE_COUNT) DOUBLES, over the dense states 1 .. N_d - 2 (collision_metrics' convention for support states: the first and the last are left
+ *              out); needs N_d >= 3:
+ *     IN_COLL 0 / 1;  NUM_COLLIDING count of cost != 0 (a NaN counts);  AVG_PENETRATION mean cost;  MAX_PENETRATION the largest cost, a NaN wins (torch.max);
+ *     FIRST_COLLIDING smallest dense index with cost != 0, -1 if none;  WORST_INDEX dense index of the maximum, the smallest on ties (and of the first NaN if any).
+ * DGP_EINVAL, nothing launched: a NULL handle or th; batch < 1; num_inter outside 0 .. 1023; all outputs NULL; dense_cost or summary without sdf; summary with N_d < 3.
+ * Every num_states and dof a handle accepts is accepted.  The sums, maxima, counts and indices of a trajectory are reduced inside its wavefront in a fixed order (no
+ * atomics): bit-identical from run to run, for either grid layout and wherever the trajectory sits in the batch.  One launch, nothing allocated or synchronised:
+ * capturable in a HIP graph. */
+#define DGP_DENSE_IN_COLL          0
+#define DGP_DENSE_NUM_COLLIDING    1
+#define DGP_DENSE_AVG_PENETRATION  2
+#define DGP_DENSE_MAX_PENETRATION  3
+#define DGP_DENSE_FIRST_COLLIDING  4
+#define DGP_DENSE_WORST_INDEX      5
+#define DGP_DENSE_COUNT            6
+int dgp_gp_interpolate(const DgpHandle* h, int32_t batch, const void* th, int32_t num_inter, const DgpSdf* sdf, double eps,
+                       void* th_dense, void* dense_cost, double* summary, void* stream);
+
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
  * hipExtLaunchKernelGGL does -- hipEventElapsedTime(start, stop) is then that kernel's execution time, the quantity
