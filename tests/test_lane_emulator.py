@@ -172,3 +172,34 @@ def test_emul_long_trajectories(be, golden):
 
 def test_emul_long_trajectories_f32(be, golden):
   PC.case_long_trajectories(be, golden, 'f32', configs=[(2, 300, 'static', {})])
+
+
+# ---- call forms (tests/call_forms.py): optional pointers NULL and buffers off the 16-byte boundary must not change a result -- the GPU test's case trimmed to three
+# trajectories on twelve (configuration, entry-point group) pairs: the forced shapes (16,4) exact and ragged, (16,2) at d = 6 and (64,1); static, per-state and scalar
+# covariances; both I/O types; one n = 257.  The SOURCE satisfies the invariants exactly (this test); whether every compiled instantiation does is test_hip_call_forms.py's.
+import call_forms as CF
+
+_CF_EMUL = [
+  (CF.Cfg(2, 'f64', (16, 4), 64, 'static', grid='per', B=3), ('forward', 'backward')),
+  (CF.Cfg(2, 'f64', (16, 4), 64, 'static', grid='shared16', B=3), ('errs',)),
+  (CF.Cfg(2, 'f64', (16, 4), 61, 'static', grid='shared1', B=3), ('loop',)),
+  (CF.Cfg(2, 'f32', (16, 4), 61, 'perstate', grid='per', B=3), ('backward',)),
+  (CF.Cfg(2, 'f32', (16, 4), 64, 'scalar', grid='shared1', B=3), ('forward', 'errs')),
+  (CF.Cfg(3, 'f64', (16, 2), 29, 'static', grid='per', B=3), ('loop',)),
+  (CF.Cfg(3, 'f32', (16, 2), 29, 'perstate', grid='shared16', B=3), ('backward',)),
+  (CF.Cfg(3, 'f64', (16, 2), 29, 'scalar', grid='shared1', B=3), ('errs',)),
+  (CF.Cfg(2, 'f64', (64, 1), 64, 'perstate', grid='shared1', B=3), ('backward',)),
+  (CF.Cfg(2, 'f32', (64, 1), 64, 'static', grid='per', B=3), ('forward',)),
+  (CF.Cfg(3, 'f32', (16, 4), 64, 'static', grid='shared1', B=3), ('errs',)),
+  (CF.long_configs('f64')[0], ('forward', 'backward')),
+]
+
+
+@pytest.mark.parametrize('i', range(len(_CF_EMUL)), ids=lambda i: ('%s-%s' % (_CF_EMUL[i][0].tag(), '+'.join(_CF_EMUL[i][1]))).replace(' ', '_'))
+def test_emul_call_forms(i):
+  c, groups = _CF_EMUL[i]
+  b = harness.Backend('emul')
+  fails = []
+  compared = CF.run_config(b, c, groups, fails)
+  assert b.guard_checks > 0 and b.input_checks > 0 and compared > 0
+  assert not fails, '%d call forms differ from the canonical call:\n' % len(fails) + '\n'.join(map(str, fails[:40]))

@@ -181,6 +181,68 @@ def test_training_iteration_xyh_robot_two_launch_backward():
     assert rel_err(a_.cpu().numpy(), b_.cpu().numpy()) < 1e-9
 
 
+def test_training_iteration_on_unaligned_slices_xyh_robot():
+  """The (x, y, theta) robot in fp32 with an odd number of states, every input a `big[1:]` slice of a larger tensor: contiguous, but the slice of a d = 6 fp32 tensor
+  starts 24 bytes past a boundary, so the launches take the scalar row / block accesses (dgp_host.h: vec_io, vec_mu, vec_qc).  forward_with_errors + backward must
+  give the bits of the same call on fresh, aligned copies -- every output and every gradient -- and a call in which only SOME inputs require grad (NULL gradient
+  pointers: the covariances alone, the learned-covariance loop; th alone, a TBPTT link) the bits of the full call, aligned or not.  (The grid takes no gradient here:
+  a shared grid's is summed by atomics, the one quantity whose bits move from run to run.)"""
+  from dgpmp2_amd.robot_models import PointRobotXYH
+  from dgpmp2_amd.gpmp2 import DiffGPMP2Planner
+  B, n, G = 5, 41, 64
+  f32 = torch.float32
+  gp, ob, pp, op, ev = ref_params(n)
+  gp.update(Q_c_inv=torch.eye(3, dtype=torch.float64), K_d=torch.tensor(0.05, dtype=torch.float64))
+  pp.update(dof=3, state_dim=6, non_holonomic=True)
+  robot = PointRobotXYH(torch.tensor(0.4, dtype=torch.float64), use_cuda=True, batch_size=B, num_traj_states=n)
+  pl = DiffGPMP2Planner(gp, ob, pp, op, ev, robot, batch_size=B, use_cuda=True).plan_layer
+  rs = np.random.RandomState(14)
+  start = np.zeros((B, 1, 6)); goal = np.zeros((B, 1, 6))
+  start[:, 0, :2] = rs.uniform(-4, 4, (B, 2)); goal[:, 0, :2] = rs.uniform(-4, 4, (B, 2)); goal[:, 0, 2] = rs.uniform(-1, 1, B)
+  th = O.straight_line_trajb(start[:, :, :3], goal[:, :, :3], 10.0, n - 1, 3) + 0.05 * rs.randn(B, n, 6)
+  A = rs.randn(B, n - 1, 3, 3) * 0.2
+  vals = dict(th=th, start=start, goal=goal, qc=np.eye(3) + A @ np.swapaxes(A, -1, -2), ow=rs.uniform(50, 2e4, (B, n, 1, 1)), eps=rs.uniform(0.1, 0.6, (B, n, 1, 1)),
+              c_dth=rs.randn(B, n, 6), c_e=rs.randn(B, 1, 1))
+  grid = T(O.circles_sdf(G, O.C2_CIRCLES), f32)
+
+  def sliced(v):
+    """big[1:] of a tensor with one more leading row; where that happens to land on a boundary (9 (n - 1) floats per row of qc), one element into a flat buffer"""
+    v = T(v, f32)
+    big = torch.empty((v.shape[0] + 1,) + tuple(v.shape[1:]), dtype=f32, device=DEV)
+    s = big[1:]
+    if s.data_ptr() % 16 == 0: s = torch.empty(v.numel() + 1, dtype=f32, device=DEV)[1:].view(v.shape)
+    s.copy_(v)
+    assert s.is_contiguous() and s.data_ptr() % 16 != 0
+    return s
+
+  def fresh(v):
+    t = T(v, f32).clone()
+    assert t.data_ptr() % 16 == 0
+    return t
+  every = ('th', 'start', 'goal', 'qc', 'ow', 'eps')
+
+  def run(make, names):
+    L = {k: make(v) for k, v in vals.items()}
+    for k in names: L[k].requires_grad_(True)
+    flat = make(grid.reshape(1, -1)[0].cpu().numpy())
+    sdf = flat.view(1, 1, G, G).expand(B, 1, G, G)
+    outs = pl.forward_with_errors(L['th'], L['start'], L['goal'], None, sdf, L['qc'], L['ow'], L['eps'])
+    dth, _, eex, sg, gp_, ob_ = outs
+    loss = (dth * L['c_dth']).sum() + (eex * L['c_e']).sum() + (sg * L['c_e'].view(B, 1)).sum() + (gp_ * L['c_e']).sum() + (ob_ * L['c_e']).sum()
+    grads = torch.autograd.grad(loss, [L[k] for k in names])
+    return [o.detach() for o in (dth, eex, sg, gp_, ob_)], dict(zip(names, grads))
+  out_a, full_a = run(fresh, every)
+  out_s, full_s = run(sliced, every)
+  assert all(torch.isfinite(o).all() for o in out_a) and all(torch.isfinite(g_).all() for g_ in full_a.values())
+  for name, a_, s_ in zip(('dtheta', 'err_ext', 'unw_sg', 'unw_gp', 'unw_obs'), out_a, out_s): assert torch.equal(a_, s_), name
+  for k in every: assert torch.equal(full_a[k], full_s[k]), k
+  for names in (('qc', 'ow', 'eps'), ('th',), ('start', 'goal'), ('eps',), ('th', 'qc')):
+    for make, tag in ((fresh, 'aligned'), (sliced, 'sliced')):
+      o_, part = run(make, names)
+      for a_, s_ in zip(out_a, o_): assert torch.equal(a_, s_), (names, tag)
+      for k in names: assert torch.equal(part[k], full_a[k]), (names, tag, k)
+
+
 def test_training_iteration_is_capturable_in_a_hip_graph(golden):
   """One iteration of the training loop -- step_with_errors with learned per-state covariances + the backward of all four outputs w.r.t. the trajectory
   and the three covariance tensors (learning/train_planner.py:311-327, 366) -- captured in a HIP graph: forward AND backward launches are recorded
