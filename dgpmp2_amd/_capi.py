@@ -31,6 +31,12 @@ DENSE_NAMES = ('in_coll', 'num_colliding', 'avg_penetration', 'max_penetration',
 DGP_DENSE_IN_COLL, DGP_DENSE_NUM_COLLIDING, DGP_DENSE_AVG_PENETRATION, DGP_DENSE_MAX_PENETRATION, DGP_DENSE_FIRST_COLLIDING, DGP_DENSE_WORST_INDEX = range(6)
 DGP_DENSE_COUNT = len(DENSE_NAMES)
 DGP_MAX_NUM_INTER = 1023
+# entries of dgp_step_loss' (DGP_LOSS_COUNT) float64 terms (one_step_loss's return order) and columns of its (B, DGP_LOSS_PER_TRAJ) float64 per_traj
+LOSS_NAMES = ('total', 'pos', 'vel', 'cov', 'gp', 'sg', 'obs', 'ext')
+DGP_LOSS_TOTAL, DGP_LOSS_POS, DGP_LOSS_VEL, DGP_LOSS_COV, DGP_LOSS_GP, DGP_LOSS_SG, DGP_LOSS_OBS, DGP_LOSS_EXT = range(8)
+DGP_LOSS_COUNT = len(LOSS_NAMES)
+LOSS_PER_TRAJ_NAMES = ('pos', 'vel', 'gp', 'sg', 'obs')
+DGP_LOSS_PER_TRAJ = len(LOSS_PER_TRAJ_NAMES)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DGP_LIB_PATH') or os.path.join(_HERE, 'lib', 'libdgpmp2_hip.so')   # override: tuning builds only
@@ -69,6 +75,10 @@ class DgpPathParams(C.Structure):
   _fields_ = [('clearance', C.c_double), ('max_sweeps', C.c_int32), ('path_cap', C.c_int32)]
 
 
+class DgpLossWeights(C.Structure):
+  _fields_ = [('vel_loss_lambda', C.c_double), ('ext_obs_lambda', C.c_double), ('ext_loss_weight', C.c_double)]
+
+
 class DgpError(RuntimeError):
   def __init__(self, code, msg):
     super(DgpError, self).__init__('dgpmp2_hip error %d: %s' % (code, msg))
@@ -80,7 +90,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'gp_interpolate', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -153,6 +163,13 @@ class CApi(object):
     if self.gp_interpolate is not None:
       self.gp_interpolate.restype = C.c_int
       self.gp_interpolate.argtypes = [vp, i32, vp, i32, C.POINTER(DgpSdf), dbl, vp, vp, vp, vp]
+    # dgp_step_loss / dgp_step_loss_backward: no twin in the emulator either
+    self.step_loss = getattr(self.lib, prefix + 'step_loss', None)
+    self.step_loss_backward = getattr(self.lib, prefix + 'step_loss_backward', None)
+    if self.step_loss is not None:
+      self.step_loss.restype = self.step_loss_backward.restype = C.c_int
+      self.step_loss.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DgpLossWeights), vp, vp, vp]
+      self.step_loss_backward.argtypes = [i32, i32, i32, i32, vp, vp, vp, C.POINTER(DgpLossWeights), vp, vp, vp, vp, vp, vp, vp, vp]
     self.time_next_launch = f('time_next_launch'); self.time_next_launch.restype = C.c_int; self.time_next_launch.argtypes = [vp, vp]
     self.event_create = f('event_create'); self.event_create.restype = C.c_int; self.event_create.argtypes = [C.POINTER(vp)]
     self.event_destroy = f('event_destroy'); self.event_destroy.restype = None; self.event_destroy.argtypes = [vp]
@@ -211,7 +228,7 @@ import sysconfig
 # never loaded by mistake
 PYCALL_PATH = os.path.join(_HERE, 'lib', '_dgp_pycall' + (sysconfig.get_config_var('EXT_SUFFIX') or '.so'))
 _PYCALL_ENTRIES = ('gn_step', 'gn_solve', 'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward',
-                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'traj_metrics', 'gp_interpolate')
+                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'traj_metrics', 'gp_interpolate', 'step_loss', 'step_loss_backward')
 
 
 def get_api():
@@ -265,6 +282,14 @@ class CtypesPycall(object):
     # (handle, batch, th, num_inter, the seven DgpSdf fields, eps, th_dense, dense_cost, summary, stream)
     return self.api.gp_interpolate(a[0], a[1], a[2], int(a[3]), self._sdf(a, 4), *a[11:])
 
+  def step_loss(self, *a):
+    # (dtype, batch, num_states, dof, update, target, target_sub, unw_sg, unw_gp, unw_obs, the three DgpLossWeights fields, terms, per_traj, stream)
+    return self.api.step_loss(*a[:10], C.byref(DgpLossWeights(float(a[10]), float(a[11]), float(a[12]))), *a[13:])
+
+  def step_loss_backward(self, *a):
+    # (dtype, batch, num_states, dof, update, target, target_sub, the three DgpLossWeights fields, g_total, the six gradient outputs, stream)
+    return self.api.step_loss_backward(*a[:7], C.byref(DgpLossWeights(float(a[7]), float(a[8]), float(a[9]))), *a[10:])
+
 
 def get_pycall():
   """The METH_FASTCALL trampoline onto the product library's entry points (csrc/dgp_pycall.c): the same C-ABI calls as the ctypes
@@ -290,6 +315,29 @@ def get_pycall():
                     % (os.path.basename(PYCALL_PATH), type(e).__name__, e))
       _pycall = CtypesPycall(api)
   return _pycall
+
+
+def step_loss(dtype, batch, num_states, dof, update, target, weights, terms, per_traj, target_sub=None, unw_sg=None, unw_gp=None, unw_obs=None, stream=None, api=None):
+  """dgp_step_loss (no handle): terms (DGP_LOSS_COUNT) and per_traj (B, DGP_LOSS_PER_TRAJ) float64 from update / target / target_sub (B,n,d) and the three (B) error
+  arrays of `dtype` (raw addresses; positions are columns [0, dof), velocities [dof, 2 dof)); weights: a DgpLossWeights or (vel_loss_lambda, ext_obs_lambda,
+  ext_loss_weight).  Two stream-ordered launches."""
+  api = api if api is not None else get_api()
+  if api.step_loss is None:
+    raise NotImplementedError('%s does not export %sstep_loss (the CPU emulator has no twin of the loss kernels)' % (api.path, api.prefix))
+  w = weights if isinstance(weights, DgpLossWeights) or weights is None else DgpLossWeights(*[float(v) for v in weights])
+  api.check(api.step_loss(int(dtype), int(batch), int(num_states), int(dof), update, target, target_sub, unw_sg, unw_gp, unw_obs, C.byref(w) if w is not None else None,
+                          terms, per_traj, stream))
+
+
+def step_loss_backward(dtype, batch, num_states, dof, update, target, weights, target_sub=None, g_total=None, g_update=None, g_target=None, g_target_sub=None,
+                       g_unw_sg=None, g_unw_gp=None, g_unw_obs=None, stream=None, api=None):
+  """dgp_step_loss_backward (no handle): the gradients of the total loss, scaled by the device scalar *g_total (None: 1.0); every output may be None.  One launch."""
+  api = api if api is not None else get_api()
+  if api.step_loss_backward is None:
+    raise NotImplementedError('%s does not export %sstep_loss_backward (the CPU emulator has no twin of the loss kernels)' % (api.path, api.prefix))
+  w = weights if isinstance(weights, DgpLossWeights) or weights is None else DgpLossWeights(*[float(v) for v in weights])
+  api.check(api.step_loss_backward(int(dtype), int(batch), int(num_states), int(dof), update, target, target_sub, C.byref(w) if w is not None else None, g_total,
+                                   g_update, g_target, g_target_sub, g_unw_sg, g_unw_gp, g_unw_obs, stream))
 
 
 def make_config(num_states, dof, io_dtype, total_time_sec, x_lims, y_lims, K_s, K_g, reg, sphere_radius, Q_c_inv,

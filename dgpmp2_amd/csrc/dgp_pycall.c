@@ -42,6 +42,12 @@ typedef int (*traj_metrics_fn)(const DgpHandle*, int32_t, const void*, const Dgp
 static traj_metrics_fn f_traj_metrics;
 typedef int (*gp_interpolate_fn)(const DgpHandle*, int32_t, const void*, int32_t, const DgpSdf*, double, void*, void*, double*, void*);
 static gp_interpolate_fn f_gp_interpolate;
+typedef int (*step_loss_fn)(int32_t, int32_t, int32_t, int32_t, const void*, const void*, const void*, const void*, const void*, const void*, const DgpLossWeights*, double*,
+                            double*, void*);
+static step_loss_fn f_step_loss;
+typedef int (*step_loss_bwd_fn)(int32_t, int32_t, int32_t, int32_t, const void*, const void*, const void*, const DgpLossWeights*, const double*, void*, void*, void*, void*,
+                                void*, void*, void*);
+static step_loss_bwd_fn f_step_loss_bwd;
 static square_covs_fn f_square_covs;
 static square_covs_bwd_fn f_square_covs_bwd;
 typedef int (*sum_partial_grids_fn)(const void*, int32_t, int32_t, int64_t, double, void*, int32_t, void*);
@@ -91,7 +97,7 @@ static inline int64_t as_i64(PyObject* o, int* bad) {
   const DgpSdf* sdfp = sdf.data ? &sdf : NULL
 
 static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
-  NEED(14, "bind");
+  NEED(16, "bind");
   f_gn_step = (gn_step_fn)P(0);
   f_gn_solve = (gn_solve_fn)P(1);
   f_eval_errors = (eval_errors_fn)P(2);
@@ -106,6 +112,8 @@ static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
   f_square_covs_bwd = (square_covs_bwd_fn)P(11);
   f_traj_metrics = (traj_metrics_fn)P(12);
   f_gp_interpolate = (gp_interpolate_fn)P(13);
+  f_step_loss = (step_loss_fn)P(14);
+  f_step_loss_bwd = (step_loss_bwd_fn)P(15);
   if (bad) return NULL;
   Py_RETURN_NONE;
 }
@@ -307,9 +315,45 @@ static PyObject* py_gp_interpolate(PyObject* self, PyObject* const* a, Py_ssize_
   return PyLong_FromLong(f_gp_interpolate(h, batch, th, num_inter, sdf.data ? &sdf : NULL, eps, th_dense, dense_cost, (double*)summary, stream));
 }
 
+/* the three weights of DgpLossWeights as Python floats, from a[i] on */
+static int loss_weights(PyObject* const* a, int i, DgpLossWeights* w) {
+  w->vel_loss_lambda = PyFloat_AsDouble(a[i]);
+  w->ext_obs_lambda = PyFloat_AsDouble(a[i + 1]);
+  w->ext_loss_weight = PyFloat_AsDouble(a[i + 2]);
+  return PyErr_Occurred() ? -1 : 0;
+}
+
+/* step_loss(dtype, batch, num_states, dof, update, target, target_sub, unw_sg, unw_gp, unw_obs, vel_loss_lambda, ext_obs_lambda, ext_loss_weight, terms, per_traj, stream) */
+static PyObject* py_step_loss(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
+  NEED(16, "step_loss");
+  BOUND(f_step_loss);
+  const int32_t dt = (int32_t)I(0), B = (int32_t)I(1), n = (int32_t)I(2), dof = (int32_t)I(3);
+  const void *upd = P(4), *tgt = P(5), *sub = P(6), *usg = P(7), *ugp = P(8), *uobs = P(9);
+  DgpLossWeights w;
+  if (loss_weights(a, 10, &w)) return NULL;
+  void *terms = P(13), *per = P(14), *stream = P(15);
+  if (bad) return NULL;
+  return PyLong_FromLong(f_step_loss(dt, B, n, dof, upd, tgt, sub, usg, ugp, uobs, &w, (double*)terms, (double*)per, stream));
+}
+
+/* step_loss_backward(dtype, batch, num_states, dof, update, target, target_sub, vel_loss_lambda, ext_obs_lambda, ext_loss_weight, g_total, g_update, g_target, g_target_sub,
+ *                    g_unw_sg, g_unw_gp, g_unw_obs, stream) */
+static PyObject* py_step_loss_bwd(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
+  NEED(18, "step_loss_backward");
+  BOUND(f_step_loss_bwd);
+  const int32_t dt = (int32_t)I(0), B = (int32_t)I(1), n = (int32_t)I(2), dof = (int32_t)I(3);
+  const void *upd = P(4), *tgt = P(5), *sub = P(6);
+  DgpLossWeights w;
+  if (loss_weights(a, 7, &w)) return NULL;
+  const void* g = P(10);
+  void *gu = P(11), *gt = P(12), *gs = P(13), *gsg = P(14), *ggp = P(15), *gobs = P(16), *stream = P(17);
+  if (bad) return NULL;
+  return PyLong_FromLong(f_step_loss_bwd(dt, B, n, dof, upd, tgt, sub, &w, (const double*)g, gu, gt, gs, gsg, ggp, gobs, stream));
+}
+
 static PyMethodDef methods[] = {
     {"bind", (PyCFunction)(void (*)(void))py_bind, METH_FASTCALL,
-     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward, traj_metrics, gp_interpolate): "
+     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward, traj_metrics, gp_interpolate, step_loss, step_loss_backward): "
      "addresses of the C-ABI entry points"},
     {"gn_solve_traced", (PyCFunction)(void (*)(void))py_gn_solve_traced, METH_FASTCALL, "dgp_gn_solve_traced"},
     {"gn_solve_backward", (PyCFunction)(void (*)(void))py_gn_solve_backward, METH_FASTCALL, "dgp_gn_solve_backward"},
@@ -320,6 +364,8 @@ static PyMethodDef methods[] = {
     {"square_covariances_backward", (PyCFunction)(void (*)(void))py_square_covs_bwd, METH_FASTCALL, "dgp_square_covariances_backward"},
     {"traj_metrics", (PyCFunction)(void (*)(void))py_traj_metrics, METH_FASTCALL, "dgp_traj_metrics"},
     {"gp_interpolate", (PyCFunction)(void (*)(void))py_gp_interpolate, METH_FASTCALL, "dgp_gp_interpolate"},
+    {"step_loss", (PyCFunction)(void (*)(void))py_step_loss, METH_FASTCALL, "dgp_step_loss"},
+    {"step_loss_backward", (PyCFunction)(void (*)(void))py_step_loss_bwd, METH_FASTCALL, "dgp_step_loss_backward"},
     {"gn_step", (PyCFunction)(void (*)(void))py_gn_step, METH_FASTCALL, "dgp_gn_step"},
     {"gn_solve", (PyCFunction)(void (*)(void))py_gn_solve, METH_FASTCALL, "dgp_gn_solve"},
     {"eval_errors", (PyCFunction)(void (*)(void))py_eval_errors, METH_FASTCALL, "dgp_eval_errors"},

@@ -1,5 +1,5 @@
 // dgp_status.h -- what every translation unit behind the C-ABI shares per calling thread (no HIP in here): the text of dgp_last_error and the pending
-// dgp_time_next_launch request.  On its own for the units that need nothing of the solver (sdf_edt.hip, obstacle_maps.hip); dgp_host.h includes it for the rest.
+// dgp_time_next_launch request.  On its own for the units that need nothing of the solver (sdf_edt.hip, obstacle_maps.hip, step_loss.hip); dgp_host.h includes it for the rest.
 #pragma once
 #include <stdio.h>
 #include <stdarg.h>

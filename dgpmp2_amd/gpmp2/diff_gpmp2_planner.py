@@ -498,6 +498,14 @@ class DiffGPMP2Planner(nn.Module):
     torch.cuda.graph."""
     return self.plan_layer.interpolate(thb, num_inter, sdfb, eps, return_cost)
 
+  def step_loss(self, dthetab, th_currb, th_optb, errors, weights=None):
+    """The loss of one training iteration -- the reference's one_step_loss(dthetab, th_optb - th_currb, qc, obscov, *errors, ...) (learning/train_planner.py:75-120,
+    :328) -- in two launches, its backward in one: -> plan_layer.LossTerms(total, pos, vel, cov, gp, sg, obs, ext), 0-d float64 device tensors of which `total` is
+    differentiable, with `.per_sample` (B,5) (pos, vel, gp, sg, obs per trajectory).  errors = (err_sg, err_gp, err_obs) of step_with_errors; weights:
+    learn_params['optim'] by default.  Positions are columns [0, dof), velocities [dof, 2 dof): the reference's columns for dof 2 (for dof 3 its text hard-codes
+    0,1 / 2,3).  Usable inside graphed_iteration / torch.cuda.graph.  No counterpart of its own in the reference's planner."""
+    return self.plan_layer.step_loss(dthetab, th_currb, th_optb, errors, weights)
+
   def get_covariances(self, out, mode='diag_identity', learn_eps=False):
     """Learn-module output (B,1,out_dim) -> covariance tensors (diff_gpmp2_planner.py:247-290).
     fix_dynamics: obscov[, eps];  diag_identity: q^2 I;  qc_full: q q^T (dof);  q_full: q q^T (state_dim);  'diag' raises."""

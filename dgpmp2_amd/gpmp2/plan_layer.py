@@ -23,6 +23,7 @@ Differences a caller can observe (all deliberate):
     in-place edit voids it); forward() / forward_with_errors() and their backward then launch the scaled-mask static kernels (DGP_QC_SCALAR) instead of the per-state
     ones.  Same values to rounding, the gradient returned for the tensor is that of its dof x dof blocks either way; a copy of the tensor (no tag) takes the per-state path.
 """
+import collections
 import weakref
 
 import torch
@@ -625,6 +626,90 @@ class _AutoTile(torch.autograd.Function):
       return g.permute(0, 1, 2, 4, 3, 5).reshape(B, C_, Ht * 4, Wt * 4)[:, :, :H, :W], None
 
 
+class LossTerms(collections.namedtuple('LossTerms', 'total pos vel cov gp sg obs ext')):
+  """What device_step_loss returns: the eight terms of the reference's one_step_loss in its return order (learning/train_planner.py:120), 0-d float64 device tensors
+  on the storage of the one (8,) result `.raw` (no slice or cast kernels) -- `total` is differentiable, the others carry no graph (the reference only ever .item()s them) -- and
+  `.per_sample` (B, 5) float64: per trajectory the summed squared position and velocity miss (over states and columns) and the three errors (pos, vel, gp, sg, obs)."""
+  raw = per_sample = None
+
+
+def _loss_weights(weights):
+  """(vel_loss_lambda, ext_obs_lambda, ext_loss_weight) as python floats from learn_params['optim'] (or any mapping with those keys)"""
+  return _f(weights['vel_loss_lambda']), _f(weights['ext_obs_lambda']), _f(weights['ext_loss_weight'])
+
+
+def _loss_in(t, dtype):
+  """An input of the loss launches as they read it: of the launch dtype and contiguous"""
+  return t if (t is None or (t.dtype is dtype and t.is_contiguous())) else t.to(dtype).contiguous()
+
+
+class _StepLoss(torch.autograd.Function):
+  """The loss of one training iteration as ONE autograd node: forward = dgp_step_loss (two stream-ordered launches), backward = ONE dgp_step_loss_backward launch
+  that reads the incoming 0-d cotangent from device memory.  Outputs: total (differentiable), the (8,) terms and the (B, 5) per-trajectory array (not
+  differentiable: the reference only ever .item()s the other terms)."""
+
+  @staticmethod
+  def forward(ctx, pc, w, dof, update, target, target_sub, e_sg, e_gp, e_obs):
+    B, n, d = update.shape
+    dtype, dev = update.dtype, update.get_device()
+    u, t, s = update.contiguous(), _loss_in(target, dtype), _loss_in(target_sub, dtype)
+    sg, gp, ob = _loss_in(e_sg, dtype), _loss_in(e_gp, dtype), _loss_in(e_obs, dtype)
+    terms = torch.empty((_capi.DGP_LOSS_COUNT,), dtype=torch.float64, device=u.device)
+    per = torch.empty((B, _capi.DGP_LOSS_PER_TRAJ), dtype=torch.float64, device=u.device)
+    _launch(dev, pc.step_loss, _io_code(dtype), B, n, dof, u.data_ptr(), t.data_ptr(), _ptr(s), _ptr(sg), _ptr(gp), _ptr(ob), w[0], w[1], w[2], terms.data_ptr(),
+            per.data_ptr(), _raw_stream(dev))
+    ctx.pc, ctx.w, ctx.dof = pc, w, dof
+    ctx.refs = (update, target, target_sub, e_sg, e_gp, e_obs)      # shapes and dtypes of the gradients to return (the launch reads the saved tensors)
+    ctx.save_for_backward(u, t, s)
+    ctx.mark_non_differentiable(terms, per)
+    ctx.set_materialize_grads(False)
+    return terms.new_empty(()).set_(terms.untyped_storage(), 0, ()), terms, per      # terms[0], as a tensor of its own: `terms` is handed out without a graph
+
+  def _impl(ctx, g_total, _g_terms, _g_per):
+    if g_total is None: return (None,) * 9
+    u, t, s = ctx.saved_tensors
+    update, target, target_sub, e_sg, e_gp, e_obs = ctx.refs
+    need = ctx.needs_input_grad[3:]
+    B, n, d = u.shape
+    dtype, dev = u.dtype, u.get_device()
+    g = g_total if (g_total.dtype is torch.float64 and g_total.is_contiguous()) else g_total.to(torch.float64).contiguous()
+    g_u = torch.empty_like(u) if need[0] else None
+    g_t = torch.empty_like(u) if need[1] else None
+    g_s = torch.empty_like(u) if (need[2] and target_sub is not None) else None
+    errs = [u.new_empty((B,)) if (nd and e is not None) else None for nd, e in zip(need[3:], (e_sg, e_gp, e_obs))]
+    if g_u is None and g_t is None and g_s is None and errs == [None, None, None]: return (None,) * 9
+    w = ctx.w
+    _launch(dev, ctx.pc.step_loss_backward, _io_code(dtype), B, n, ctx.dof, u.data_ptr(), t.data_ptr(), _ptr(s), w[0], w[1], w[2], g.data_ptr(), _ptr(g_u), _ptr(g_t),
+            _ptr(g_s), _ptr(errs[0]), _ptr(errs[1]), _ptr(errs[2]), _raw_stream(dev))
+    back = lambda gr, ref: None if gr is None else _grad_out(gr, ref)
+    return (None, None, None, back(g_u, update), back(g_t, target), back(g_s, target_sub), back(errs[0], e_sg), back(errs[1], e_gp), back(errs[2], e_obs))
+
+  backward = _backward_of(_impl)
+
+
+def device_step_loss(pc, dof, update, target, target_sub, errors, weights):
+  """dgp_step_loss on device tensors -> LossTerms.  update, target (B,n,d) and target_sub (B,n,d) or None: the per-element miss is update - (target - target_sub);
+  errors = (err_sg, err_gp, err_obs), each with B elements or None (a zero term); weights: a mapping with 'vel_loss_lambda', 'ext_obs_lambda', 'ext_loss_weight'.
+  Positions are columns [0, dof), velocities [dof, 2 dof) (the reference hard-codes columns 0,1 / 2,3: the same for dof 2).  The tensors take update's dtype."""
+  if dof not in (2, 3): raise ValueError('dof must be 2 or 3, got %r' % (dof,))
+  if update.dim() != 3 or update.shape[2] != 2 * dof: raise ValueError('update must be (B,n,%d), got %s' % (2 * dof, tuple(update.shape)))
+  if update.dtype not in (torch.float32, torch.float64): raise TypeError('dgpmp2_amd supports float32 and float64 tensors, got %s' % update.dtype)
+  dev = update.get_device()
+  if dev < 0: _require_cuda(update, 'update')
+  B = update.shape[0]
+  if target is None: raise ValueError('target is required')
+  for name, t in (('target', target), ('target_sub', target_sub)):
+    if t is not None and t.shape != update.shape: raise ValueError('%s must have the shape of update %s, got %s' % (name, tuple(update.shape), tuple(t.shape)))
+  errors = tuple(errors) + (None,) * (3 - len(errors))
+  for name, e in zip(('err_sg', 'err_gp', 'err_obs'), errors):
+    if e is not None and e.numel() != B: raise ValueError('%s must hold one value per trajectory (%d), got %s' % (name, B, tuple(e.shape)))
+  _same_device(dev, target=target, target_sub=target_sub, err_sg=errors[0], err_gp=errors[1], err_obs=errors[2])
+  total, terms, per = _StepLoss.apply(pc, _loss_weights(weights), dof, update, target, target_sub, *errors)
+  out = LossTerms(total, *terms.unbind(0)[1:])
+  out.raw, out.per_sample = terms, per
+  return out
+
+
 class PlanLayer(nn.Module):
   """See module docstring.  Constructor mirrors plan_layer.py:14."""
 
@@ -1105,6 +1190,22 @@ class PlanLayer(nn.Module):
     from ..utils.planner_utils import gp_interpolate_times
     times = gp_interpolate_times(_f(self.total_time_sec), self.total_time_step, K, dtype=torch.float64, device=thc.device)
     return DenseTrajectory(dense, times, raw, cost)
+
+  def step_loss(self, dthetab, th_currb, th_optb, errors, weights=None):
+    """The loss of one training iteration on the device (dgp_step_loss; include/dgpmp2_hip.h states it, utils.learn_utils.one_step_loss_torch is its torch mirror):
+    the reference's one_step_loss(dthetab, th_optb - th_currb, ...) (learning/train_planner.py:75-120, :328) with the subtraction folded in -- the miss is
+    dthetab - (th_optb - th_currb) -- and one autograd node whose backward is one launch.  dthetab, th_currb, th_optb (B,n,d); errors = (err_sg, err_gp, err_obs) as
+    step_with_errors / unweighted_errors_batch return them (an entry may be None: a zero term); weights: learn_params['optim'] by default (the keys vel_loss_lambda,
+    ext_obs_lambda, ext_loss_weight).  Positions are columns [0, dof), velocities [dof, d): for dof 2 the reference's hard-coded columns 0,1 / 2,3, for dof 3 NOT
+    what the reference's text would pick (theta and v_x as "velocity", v_y and omega ignored; its training loop only runs dof 2).  -> LossTerms(total, pos, vel, cov, gp,
+    sg, obs, ext), 0-d float64 tensors (`total` differentiable w.r.t. all six inputs), with `.per_sample` (B,5) and `.raw` (8,).  Usable inside graphed_iteration /
+    torch.cuda.graph."""
+    if weights is None:
+      if self.learn_params is None or 'optim' not in self.learn_params: raise ValueError("step_loss needs `weights` (or learn_params['optim'])")
+      weights = self.learn_params['optim']
+    if dthetab.dim() != 3 or dthetab.shape[1] != self.num_traj_states or dthetab.shape[2] != self.state_dim:
+      raise ValueError('dthetab must be (B,%d,%d), got %s' % (self.num_traj_states, self.state_dim, tuple(dthetab.shape)))
+    return device_step_loss(self._pc, self.dof, dthetab, th_optb, th_currb, errors, weights)
 
   def sample_problems(self, sdfb, num_problems, params, dtype=torch.float64, env_index=None, diagonal=None, seed=0, first_problem=0):
     """Feasible start / goal pairs and their straight-line initial trajectories in ONE launch (dgp_sample_problems; datasets.problem_generation.sample_problems is the

@@ -535,6 +535,57 @@ int dgp_init_paths(const DgpHandle* h, int32_t batch, const DgpSdf* sdf, const i
 int dgp_gp_interpolate(const DgpHandle* h, int32_t batch, const void* th, int32_t num_inter, const DgpSdf* sdf, double eps,
                        void* th_dense, void* dense_cost, double* summary, void* stream);
 
+/* The loss of one training iteration and its gradient on the device: the reference's one_step_loss (learning/train_planner.py:75-120, called at :328 as
+ * one_step_loss(dthetab, th_opt_b - th_curr_b, ...)) -- eight index_select, four cat, two einsum, five mean and the scalar arithmetic around them, forward and
+ * backward -- as two stream-ordered launches forward and one launch backward.  No handle: the loss needs only dtype (DGP_F32 / DGP_F64, the type of every `void*`
+ * array below), B = batch, n = num_states and dof (2 or 3), d = 2 dof.
+ * Columns.  Positions are columns [0, dof), velocities [dof, d).  For dof 2 these are exactly the reference's columns 0, 1 / 2, 3; the reference hard-codes those
+ *   four columns whatever dof is (at dof 3 it would take theta and v_x as "velocity" and ignore v_y and omega; its training loop only ever runs dof 2).
+ * Arithmetic.  fp64 whatever dtype, FMA contraction off, every operation in the order written, left to right inside a pair of parentheses.
+ * Per-element miss.  m = (double)update - ((double)target - (double)target_sub); with target_sub == NULL, m = (double)update - (double)target.  The three-array
+ *   form folds the reference's subtraction in: update = dtheta, target = th_opt, target_sub = th_curr.
+ * Per trajectory b.  pos_b = sum_i sum_{c < dof} m^2,  vel_b = sum_i sum_{dof <= c < d} m^2;  gp_b, sg_b, obs_b = unw_gp[b], unw_sg[b], unw_obs[b] converted to
+ *   double (0 for a NULL array).  per_traj row b holds (pos_b, vel_b, gp_b, sg_b, obs_b).  The two sums are formed inside the trajectory's wavefront in a fixed
+ *   order that depends on n alone: a row has the same bits wherever the trajectory sits in the batch and whatever the batch size is.
+ * Batch.  POS = (sum_b pos_b) / ((double)B * (double)n), VEL likewise;  GP = (sum_b gp_b) / (double)B, SG and OBS likewise (fixed-order sums of per_traj, one workgroup);
+ *   EXT = (GP + SG) + ext_obs_lambda * OBS;  TOTAL = (POS + vel_loss_lambda * VEL) + ext_loss_weight * EXT;  COV = 0.
+ * terms holds them at DGP_LOSS_*: one_step_loss's return order (:120).
+ * Backward, g = *g_total (1.0 for NULL):
+ *   c_ext = ext_loss_weight * g;  k_pos = (2.0 * g) / ((double)B * (double)n);  k_vel = (2.0 * (vel_loss_lambda * g)) / ((double)B * (double)n);
+ *   g_update = m * k (k = k_pos for a position column, k_vel for a velocity column);  g_target = -(m * k);  g_target_sub = m * k;
+ *   g_unw_gp = g_unw_sg = c_ext / (double)B;  g_unw_obs = (ext_obs_lambda * c_ext) / (double)B.
+ *   Every stored value is rounded once to dtype; NULL outputs are skipped (g_target_sub may be asked for without target_sub: m is then update - target).
+ * Pointers need only be aligned to their element type: 16-byte vector accesses where every (B,n,d) pointer of the call allows them, element accesses otherwise,
+ * the same bits either way.
+ * DGP_EINVAL, nothing launched: dtype not DGP_F32 / DGP_F64; batch < 1; num_states < 1; dof not 2 or 3; a NULL update, target, w, terms or per_traj; a NaN weight;
+ * backward with every output NULL.  No atomics: bit-identical from run to run.  Nothing allocated or synchronised: capturable in a HIP graph.
+ * dgp_time_next_launch times the first of the two forward launches. */
+#define DGP_LOSS_TOTAL 0   /* one_step_loss's return order, train_planner.py:120 */
+#define DGP_LOSS_POS   1
+#define DGP_LOSS_VEL   2
+#define DGP_LOSS_COV   3   /* always 0: the reference's covariance regulariser is commented out (:113-116) */
+#define DGP_LOSS_GP    4
+#define DGP_LOSS_SG    5
+#define DGP_LOSS_OBS   6
+#define DGP_LOSS_EXT   7
+#define DGP_LOSS_COUNT 8
+#define DGP_LOSS_PER_TRAJ 5   /* per_traj columns: pos, vel, gp, sg, obs */
+typedef struct DgpLossWeights { double vel_loss_lambda, ext_obs_lambda, ext_loss_weight; } DgpLossWeights;
+
+int dgp_step_loss(int32_t dtype, int32_t batch, int32_t num_states, int32_t dof,
+                  const void* update, const void* target, const void* target_sub,       /* (B,n,d) io dtype; target_sub may be NULL */
+                  const void* unw_sg, const void* unw_gp, const void* unw_obs,         /* (B) io dtype; each may be NULL (= 0) */
+                  const DgpLossWeights* w,
+                  double* terms,        /* (DGP_LOSS_COUNT) doubles */
+                  double* per_traj,     /* (B, DGP_LOSS_PER_TRAJ) doubles: output AND workspace, required */
+                  void* stream);
+int dgp_step_loss_backward(int32_t dtype, int32_t batch, int32_t num_states, int32_t dof,
+                  const void* update, const void* target, const void* target_sub,
+                  const DgpLossWeights* w, const double* g_total,                      /* device scalar; NULL = 1.0 */
+                  void* g_update, void* g_target, void* g_target_sub,                  /* (B,n,d) io dtype; each may be NULL */
+                  void* g_unw_sg, void* g_unw_gp, void* g_unw_obs,                     /* (B) io dtype; each may be NULL */
+                  void* stream);
+
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
  * hipExtLaunchKernelGGL does -- hipEventElapsedTime(start, stop) is then that kernel's execution time, the quantity
