@@ -37,6 +37,10 @@ DGP_LOSS_TOTAL, DGP_LOSS_POS, DGP_LOSS_VEL, DGP_LOSS_COV, DGP_LOSS_GP, DGP_LOSS_
 DGP_LOSS_COUNT = len(LOSS_NAMES)
 LOSS_PER_TRAJ_NAMES = ('pos', 'vel', 'gp', 'sg', 'obs')
 DGP_LOSS_PER_TRAJ = len(LOSS_PER_TRAJ_NAMES)
+# columns of dgp_sdf_lookup's (B, DGP_LOOKUP_COUNT) float64 summary, in the header's order (DGP_LOOKUP_*)
+LOOKUP_NAMES = ('solved', 'num_blocked', 'first_blocked', 'min_dist', 'min_index')
+DGP_LOOKUP_SOLVED, DGP_LOOKUP_NUM_BLOCKED, DGP_LOOKUP_FIRST_BLOCKED, DGP_LOOKUP_MIN_DIST, DGP_LOOKUP_MIN_INDEX = range(5)
+DGP_LOOKUP_COUNT = len(LOOKUP_NAMES)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DGP_LIB_PATH') or os.path.join(_HERE, 'lib', 'libdgpmp2_hip.so')   # override: tuning builds only
@@ -90,7 +94,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -170,6 +174,13 @@ class CApi(object):
       self.step_loss.restype = self.step_loss_backward.restype = C.c_int
       self.step_loss.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DgpLossWeights), vp, vp, vp]
       self.step_loss_backward.argtypes = [i32, i32, i32, i32, vp, vp, vp, C.POINTER(DgpLossWeights), vp, vp, vp, vp, vp, vp, vp, vp]
+    # dgp_sdf_lookup / dgp_sdf_lookup_backward: no twin in the emulator either
+    self.sdf_lookup = getattr(self.lib, prefix + 'sdf_lookup', None)
+    self.sdf_lookup_backward = getattr(self.lib, prefix + 'sdf_lookup_backward', None)
+    if self.sdf_lookup is not None:
+      self.sdf_lookup.restype = self.sdf_lookup_backward.restype = C.c_int
+      self.sdf_lookup.argtypes = [i32, i32, i32, vp, i64, C.POINTER(DgpSdf), dbl, C.POINTER(dbl), C.POINTER(dbl), dbl, vp, vp, vp, vp]
+      self.sdf_lookup_backward.argtypes = [i32, i32, i32, vp, i64, C.POINTER(DgpSdf), dbl, C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp, vp, i64, i32, vp]
     self.time_next_launch = f('time_next_launch'); self.time_next_launch.restype = C.c_int; self.time_next_launch.argtypes = [vp, vp]
     self.event_create = f('event_create'); self.event_create.restype = C.c_int; self.event_create.argtypes = [C.POINTER(vp)]
     self.event_destroy = f('event_destroy'); self.event_destroy.restype = None; self.event_destroy.argtypes = [vp]
@@ -228,7 +239,7 @@ import sysconfig
 # never loaded by mistake
 PYCALL_PATH = os.path.join(_HERE, 'lib', '_dgp_pycall' + (sysconfig.get_config_var('EXT_SUFFIX') or '.so'))
 _PYCALL_ENTRIES = ('gn_step', 'gn_solve', 'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward',
-                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'traj_metrics', 'gp_interpolate', 'step_loss', 'step_loss_backward')
+                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'traj_metrics', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward')
 
 
 def get_api():
@@ -291,6 +302,17 @@ class CtypesPycall(object):
     return self.api.step_loss_backward(*a[:7], C.byref(DgpLossWeights(float(a[7]), float(a[8]), float(a[9]))), *a[10:])
 
 
+  def sdf_lookup(self, *a):
+    # (dtype, batch, num_points, points, point_stride, the seven DgpSdf fields, res, x_lo, x_hi, y_lo, y_hi, clearance, d_obs, J, summary, stream)
+    return self.api.sdf_lookup(int(a[0]), int(a[1]), int(a[2]), a[3], int(a[4]), self._sdf(a, 5), float(a[12]), (C.c_double * 2)(float(a[13]), float(a[14])),
+                               (C.c_double * 2)(float(a[15]), float(a[16])), float(a[17]), *a[18:])
+
+  def sdf_lookup_backward(self, *a):
+    # (dtype, batch, num_points, points, point_stride, the seven DgpSdf fields, res, x_lo, x_hi, y_lo, y_hi, g_d, g_J, g_points, g_sdf, g_sdf_batch_stride, g_sdf_copies, stream)
+    return self.api.sdf_lookup_backward(int(a[0]), int(a[1]), int(a[2]), a[3], int(a[4]), self._sdf(a, 5), float(a[12]), (C.c_double * 2)(float(a[13]), float(a[14])),
+                                        (C.c_double * 2)(float(a[15]), float(a[16])), a[17], a[18], a[19], a[20], int(a[21]), int(a[22]), a[23])
+
+
 def get_pycall():
   """The METH_FASTCALL trampoline onto the product library's entry points (csrc/dgp_pycall.c): the same C-ABI calls as the ctypes
   binding above at a tenth of the per-call marshalling cost.  What the torch-facing layer (dgpmp2_amd.gpmp2) launches through;
@@ -338,6 +360,30 @@ def step_loss_backward(dtype, batch, num_states, dof, update, target, weights, t
   w = weights if isinstance(weights, DgpLossWeights) or weights is None else DgpLossWeights(*[float(v) for v in weights])
   api.check(api.step_loss_backward(int(dtype), int(batch), int(num_states), int(dof), update, target, target_sub, C.byref(w) if w is not None else None, g_total,
                                    g_update, g_target, g_target_sub, g_unw_sg, g_unw_gp, g_unw_obs, stream))
+
+
+def _lims(v):
+  return None if v is None else (C.c_double * 2)(float(v[0]), float(v[1]))
+
+
+def sdf_lookup(dtype, batch, num_points, points, point_stride, sdf, res, x_lims, y_lims, clearance=0.0, d_obs=None, J=None, summary=None, stream=None, api=None):
+  """dgp_sdf_lookup (no handle): d_obs (B,S) and J (B,S,2) of `dtype` and / or summary (B, DGP_LOOKUP_COUNT) float64 of the bilinear lookup of points (B,S,>=2; row
+  pitch point_stride elements) in the grid `sdf` (a DgpSdf), raw addresses.  One launch."""
+  api = api if api is not None else get_api()
+  if api.sdf_lookup is None:
+    raise NotImplementedError('%s does not export %ssdf_lookup (the CPU emulator has no twin of the lookup kernels)' % (api.path, api.prefix))
+  api.check(api.sdf_lookup(int(dtype), int(batch), int(num_points), points, int(point_stride), C.byref(sdf) if sdf is not None else None, float(res), _lims(x_lims),
+                           _lims(y_lims), float(clearance), d_obs, J, summary, stream))
+
+
+def sdf_lookup_backward(dtype, batch, num_points, points, point_stride, sdf, res, x_lims, y_lims, g_d=None, g_J=None, g_points=None, g_sdf=None, g_sdf_batch_stride=0,
+                        g_sdf_copies=1, stream=None, api=None):
+  """dgp_sdf_lookup_backward (no handle): g_points (B,S,2) written, g_sdf accumulated with atomics (zeroed by the caller; sdf.grad_mode DGP_GSDF_DENSE / _F64).  One launch."""
+  api = api if api is not None else get_api()
+  if api.sdf_lookup_backward is None:
+    raise NotImplementedError('%s does not export %ssdf_lookup_backward (the CPU emulator has no twin of the lookup kernels)' % (api.path, api.prefix))
+  api.check(api.sdf_lookup_backward(int(dtype), int(batch), int(num_points), points, int(point_stride), C.byref(sdf) if sdf is not None else None, float(res), _lims(x_lims),
+                                    _lims(y_lims), g_d, g_J, g_points, g_sdf, int(g_sdf_batch_stride), int(g_sdf_copies), stream))
 
 
 def make_config(num_states, dof, io_dtype, total_time_sec, x_lims, y_lims, K_s, K_g, reg, sphere_radius, Q_c_inv,

@@ -48,6 +48,11 @@ static step_loss_fn f_step_loss;
 typedef int (*step_loss_bwd_fn)(int32_t, int32_t, int32_t, int32_t, const void*, const void*, const void*, const DgpLossWeights*, const double*, void*, void*, void*, void*,
                                 void*, void*, void*);
 static step_loss_bwd_fn f_step_loss_bwd;
+typedef int (*sdf_lookup_fn)(int32_t, int32_t, int32_t, const void*, int64_t, const DgpSdf*, double, const double*, const double*, double, void*, void*, double*, void*);
+static sdf_lookup_fn f_sdf_lookup;
+typedef int (*sdf_lookup_bwd_fn)(int32_t, int32_t, int32_t, const void*, int64_t, const DgpSdf*, double, const double*, const double*, const void*, const void*, void*, void*,
+                                 int64_t, int32_t, void*);
+static sdf_lookup_bwd_fn f_sdf_lookup_bwd;
 static square_covs_fn f_square_covs;
 static square_covs_bwd_fn f_square_covs_bwd;
 typedef int (*sum_partial_grids_fn)(const void*, int32_t, int32_t, int64_t, double, void*, int32_t, void*);
@@ -97,7 +102,7 @@ static inline int64_t as_i64(PyObject* o, int* bad) {
   const DgpSdf* sdfp = sdf.data ? &sdf : NULL
 
 static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
-  NEED(16, "bind");
+  NEED(18, "bind");
   f_gn_step = (gn_step_fn)P(0);
   f_gn_solve = (gn_solve_fn)P(1);
   f_eval_errors = (eval_errors_fn)P(2);
@@ -114,6 +119,8 @@ static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
   f_gp_interpolate = (gp_interpolate_fn)P(13);
   f_step_loss = (step_loss_fn)P(14);
   f_step_loss_bwd = (step_loss_bwd_fn)P(15);
+  f_sdf_lookup = (sdf_lookup_fn)P(16);
+  f_sdf_lookup_bwd = (sdf_lookup_bwd_fn)P(17);
   if (bad) return NULL;
   Py_RETURN_NONE;
 }
@@ -351,9 +358,55 @@ static PyObject* py_step_loss_bwd(PyObject* self, PyObject* const* a, Py_ssize_t
   return PyLong_FromLong(f_step_loss_bwd(dt, B, n, dof, upd, tgt, sub, &w, (const double*)g, gu, gt, gs, gsg, ggp, gobs, stream));
 }
 
+/* res, x_lims[2], y_lims[2] as Python floats, from a[i] on (five arguments) */
+static int lookup_frame(PyObject* const* a, int i, double* res, double* xl, double* yl) {
+  *res = PyFloat_AsDouble(a[i]);
+  xl[0] = PyFloat_AsDouble(a[i + 1]); xl[1] = PyFloat_AsDouble(a[i + 2]);
+  yl[0] = PyFloat_AsDouble(a[i + 3]); yl[1] = PyFloat_AsDouble(a[i + 4]);
+  return PyErr_Occurred() ? -1 : 0;
+}
+
+/* sdf_lookup(dtype, batch, num_points, points, point_stride, sdf_data, sdf_rows, sdf_cols, sdf_batch_stride, sdf_layout, sdf_grad_mode, sdf_grad_indices, res, x_lo, x_hi,
+ *            y_lo, y_hi, clearance, d_obs, J, summary, stream) */
+static PyObject* py_sdf_lookup(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
+  NEED(22, "sdf_lookup");
+  BOUND(f_sdf_lookup);
+  const int32_t dt = (int32_t)I(0), B = (int32_t)I(1), S = (int32_t)I(2);
+  const void* pts = P(3);
+  const int64_t ps = I(4);
+  DgpSdf sdf = {P(5), (int32_t)I(6), (int32_t)I(7), I(8), (int32_t)I(9), (int32_t)I(10), (int64_t*)P(11)};
+  double res, xl[2], yl[2];
+  if (lookup_frame(a, 12, &res, xl, yl)) return NULL;
+  const double clr = PyFloat_AsDouble(a[17]);
+  if (clr == -1.0 && PyErr_Occurred()) return NULL;
+  void *d = P(18), *J = P(19), *sum = P(20), *stream = P(21);
+  if (bad) return NULL;
+  return PyLong_FromLong(f_sdf_lookup(dt, B, S, pts, ps, sdf.data ? &sdf : NULL, res, xl, yl, clr, d, J, (double*)sum, stream));
+}
+
+/* sdf_lookup_backward(dtype, batch, num_points, points, point_stride, the seven DgpSdf fields, res, x_lo, x_hi, y_lo, y_hi, g_d, g_J, g_points, g_sdf,
+ *                     g_sdf_batch_stride, g_sdf_copies, stream) */
+static PyObject* py_sdf_lookup_bwd(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
+  NEED(24, "sdf_lookup_backward");
+  BOUND(f_sdf_lookup_bwd);
+  const int32_t dt = (int32_t)I(0), B = (int32_t)I(1), S = (int32_t)I(2);
+  const void* pts = P(3);
+  const int64_t ps = I(4);
+  DgpSdf sdf = {P(5), (int32_t)I(6), (int32_t)I(7), I(8), (int32_t)I(9), (int32_t)I(10), (int64_t*)P(11)};
+  double res, xl[2], yl[2];
+  if (lookup_frame(a, 12, &res, xl, yl)) return NULL;
+  const void *gd = P(17), *gJ = P(18);
+  void *gp = P(19), *gs = P(20);
+  const int64_t gstride = I(21);
+  const int32_t copies = (int32_t)I(22);
+  void* stream = P(23);
+  if (bad) return NULL;
+  return PyLong_FromLong(f_sdf_lookup_bwd(dt, B, S, pts, ps, sdf.data ? &sdf : NULL, res, xl, yl, gd, gJ, gp, gs, gstride, copies, stream));
+}
+
 static PyMethodDef methods[] = {
     {"bind", (PyCFunction)(void (*)(void))py_bind, METH_FASTCALL,
-     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward, traj_metrics, gp_interpolate, step_loss, step_loss_backward): "
+     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward, traj_metrics, gp_interpolate, step_loss, step_loss_backward, sdf_lookup, sdf_lookup_backward): "
      "addresses of the C-ABI entry points"},
     {"gn_solve_traced", (PyCFunction)(void (*)(void))py_gn_solve_traced, METH_FASTCALL, "dgp_gn_solve_traced"},
     {"gn_solve_backward", (PyCFunction)(void (*)(void))py_gn_solve_backward, METH_FASTCALL, "dgp_gn_solve_backward"},
@@ -366,6 +419,8 @@ static PyMethodDef methods[] = {
     {"gp_interpolate", (PyCFunction)(void (*)(void))py_gp_interpolate, METH_FASTCALL, "dgp_gp_interpolate"},
     {"step_loss", (PyCFunction)(void (*)(void))py_step_loss, METH_FASTCALL, "dgp_step_loss"},
     {"step_loss_backward", (PyCFunction)(void (*)(void))py_step_loss_bwd, METH_FASTCALL, "dgp_step_loss_backward"},
+    {"sdf_lookup", (PyCFunction)(void (*)(void))py_sdf_lookup, METH_FASTCALL, "dgp_sdf_lookup"},
+    {"sdf_lookup_backward", (PyCFunction)(void (*)(void))py_sdf_lookup_bwd, METH_FASTCALL, "dgp_sdf_lookup_backward"},
     {"gn_step", (PyCFunction)(void (*)(void))py_gn_step, METH_FASTCALL, "dgp_gn_step"},
     {"gn_solve", (PyCFunction)(void (*)(void))py_gn_solve, METH_FASTCALL, "dgp_gn_solve"},
     {"eval_errors", (PyCFunction)(void (*)(void))py_eval_errors, METH_FASTCALL, "dgp_eval_errors"},

@@ -506,6 +506,12 @@ class DiffGPMP2Planner(nn.Module):
     0,1 / 2,3).  Usable inside graphed_iteration / torch.cuda.graph.  No counterpart of its own in the reference's planner."""
     return self.plan_layer.step_loss(dthetab, th_currb, th_optb, errors, weights)
 
+  def check_solved(self, thb, sdfb, clearance=None):
+    """The verdict of the reference's check_solved (learning/train_initializer.py:81-88) for every trajectory of the batch in one launch: -> (B,) bool device
+    tensor, True where no state has a signed distance <= clearance (the sphere radius by default) at its position; the resolution comes from sdfb's padded width, as
+    in the planner's obstacle factor.  No autograd, no synchronisation; does not depend on the planner's num_states."""
+    return self.plan_layer.check_solved(thb, sdfb, clearance)
+
   def get_covariances(self, out, mode='diag_identity', learn_eps=False):
     """Learn-module output (B,1,out_dim) -> covariance tensors (diff_gpmp2_planner.py:247-290).
     fix_dynamics: obscov[, eps];  diag_identity: q^2 I;  qc_full: q q^T (dof);  q_full: q q^T (state_dim);  'diag' raises."""

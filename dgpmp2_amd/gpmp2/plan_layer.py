@@ -1207,6 +1207,28 @@ class PlanLayer(nn.Module):
       raise ValueError('dthetab must be (B,%d,%d), got %s' % (self.num_traj_states, self.state_dim, tuple(dthetab.shape)))
     return device_step_loss(self._pc, self.dof, dthetab, th_optb, th_currb, errors, weights)
 
+  def check_solved(self, thb, sdfb, clearance=None):
+    """Whether every state of a trajectory keeps clear of the obstacles, for the whole batch in ONE launch (dgp_sdf_lookup's summary; the test of the reference's
+    check_solved, learning/train_initializer.py:81-88): -> (B,) bool device tensor, True where NO state has a signed distance d_obs <= clearance at its position.
+    thb (B,n,d), read in place; sdfb as for forward() (row-major, TiledSdf, expand()ed shared grids); clearance: the sphere radius by default.  The resolution is
+    taken from the padded width of sdfb, as the planner's own obstacle factor takes it (obstacle_cost.py:34) -- utils.learn_utils.check_solved takes the
+    reference's explicit cell size instead.  Unlike trajectory_metrics' in_collision, the first and the last state count, and the threshold carries no epsilon.
+    Does not depend on num_traj_states.  No autograd, no synchronisation; usable inside torch.cuda.graph."""
+    from .sdf_lookup import device_sdf_lookup
+    if thb.dim() != 3 or thb.shape[2] < 2: raise ValueError('thb must be (B,n,d), got %s' % (tuple(thb.shape),))
+    if sdfb is None: raise ValueError('check_solved needs the signed-distance grids (sdfb)')
+    hw = sdfb.__dict__.get('_dgp_hw') if sdfb.dim() == 6 else None
+    W = int(hw[1]) if hw is not None else int(sdfb.shape[-1])
+    if sdfb.dim() == 6 and hw is None:
+      if self.sdf_hw is None: raise ValueError('tiled sdfb carries no logical grid size (utils.sdf_utils.TiledSdf) and plan_layer.sdf_hw is not set')
+      from ..utils.sdf_utils import as_tiled
+      sdfb, W = as_tiled(sdfb, self.sdf_hw), int(self.sdf_hw[1])
+    x_lims, y_lims = [_f(v) for v in self.env_params['x_lims']], [_f(v) for v in self.env_params['y_lims']]
+    res = (x_lims[1] - x_lims[0]) / W
+    r = _f(self.robot_model.get_sphere_radii()) if clearance is None else _f(clearance)
+    if sdfb.dtype is not thb.dtype: sdfb = sdfb.to(thb.dtype)
+    return device_sdf_lookup(sdfb, thb, res, x_lims, y_lims, r, want_d=False, want_J=False).solved
+
   def sample_problems(self, sdfb, num_problems, params, dtype=torch.float64, env_index=None, diagonal=None, seed=0, first_problem=0):
     """Feasible start / goal pairs and their straight-line initial trajectories in ONE launch (dgp_sample_problems; datasets.problem_generation.sample_problems is the
     documented front end and fills `params`, a _capi.DgpSampleParams).  sdfb as for forward() (row-major, TiledSdf, a shared grid); env_index (B) int32 device tensor:

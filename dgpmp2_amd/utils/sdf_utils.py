@@ -165,6 +165,80 @@ def sdf_2d_batch(images, padlen=1, res=1.0, dtype=None, layout='rowmajor'):
   return out[0] if squeeze else (out.unsqueeze(1) if channel else out)
 
 
+def _rowmajor_grids(imb):
+  """imb as (B | 1, H, W) row-major grids for the torch mirror: (B,1,H,W), (B,H,W) or a TiledSdf."""
+  if imb.dim() == 6: imb = untile_sdf(imb)
+  if imb.dim() == 4:
+    if imb.shape[1] != 1: raise ValueError('imb must have one channel, got %s' % (tuple(imb.shape),))
+    imb = imb[:, 0]
+  if imb.dim() != 3: raise ValueError('imb must be (B,1,H,W), (B,H,W) or the tiles of tile_sdf, got %s' % (tuple(imb.shape),))
+  return imb[0:1] if (imb.shape[0] > 1 and imb.stride(0) == 0) else imb      # an expand()ed shared grid: the one grid (no B-fold copy in a dtype conversion)
+
+
+def bilinear_interpolate_torch(imb, stateb, res, x_lims, y_lims):
+  """The reference's bilinear_interpolate (utils/sdf_utils.py:38-107) in plain torch ops, this project's own statement of it, written from oracle/gpmp2_oracle.py:
+  runs anywhere (CPU included), differentiable by autograd w.r.t. imb and stateb; the mirror the device lookup is tested and timed against.  The arithmetic is
+  float64 in the oracle's operation order whatever the input dtype (float64 inputs: the oracle's bits); both outputs are cast once to stateb's dtype.  The quirks
+  of the reference are kept: x2 = x1 + 1 before clamping, clamped integers against unclamped pixel coordinates in the weights, and no in-limits rule (a no-op on
+  torch >= 1.2).  floor() is saturated to +-1e9 before the integer conversion and a NaN takes index 0, as the kernels do.
+  imb (B,1,H,W) / (B,H,W) / a TiledSdf, one grid or an expand()ed view shared by all rows; stateb (B,S,2) -> d_obs (B,S,1), J (B,S,2)."""
+  import torch
+  if imb.dtype is not stateb.dtype or not stateb.dtype.is_floating_point: raise TypeError('imb (%s) and stateb (%s) must share a floating dtype' % (imb.dtype, stateb.dtype))
+  g = _rowmajor_grids(imb).to(torch.float64)
+  B, S = stateb.shape[0], stateb.shape[1]
+  if g.shape[0] not in (1, B): raise ValueError('imb has %d grids for a batch of %d rows of points' % (g.shape[0], B))
+  H, W = g.shape[-2], g.shape[-1]
+  res = float(res)
+  st = stateb.to(torch.float64)
+  ox = (0. - float(x_lims[0]) / res)
+  oy = (0. - float(y_lims[0]) / res)
+  px = (ox + st[:, :, 0] / res).reshape(-1)
+  py = (oy - st[:, :, 1] / res).reshape(-1)
+
+  def cell(p, hi):
+    f = torch.floor(p.detach())
+    f = torch.where(torch.isnan(f), torch.full_like(f, -1.0e9), torch.clamp(f, -1.0e9, 1.0e9)).to(torch.int64)
+    return torch.clamp(f, 0, hi), torch.clamp(f + 1, 0, hi)
+  x1, x2 = cell(px, W - 1)
+  y1, y2 = cell(py, H - 1)
+  pz = torch.arange(B, device=st.device).repeat_interleave(S) if g.shape[0] != 1 else torch.zeros(B * S, dtype=torch.int64, device=st.device)
+  a, b, c, e = g[pz, y1, x1], g[pz, y1, x2], g[pz, y2, x1], g[pz, y2, x2]
+  fx1, fx2, fy1, fy2 = x1.to(torch.float64), x2.to(torch.float64), y1.to(torch.float64), y2.to(torch.float64)
+  wja = fy2 - py; wjb = py - fy1; wjc = fx2 - px; wjd = px - fx1
+  wa = wjc * wja; wb = wjd * wja; wc = wjc * wjb; wd = wjd * wjb
+  d = wa * a + wb * b + wc * c + wd * e
+  J0 = -1.0 * (wja * (b - a) + wjb * (e - c)) / res
+  J1 = (wjc * (c - a) + wjd * (e - b)) / res
+  return d.reshape(B, S, 1).to(stateb.dtype), torch.stack((J0, J1), -1).reshape(B, S, 2).to(stateb.dtype)
+
+
+def bilinear_interpolate(imb, stateb, res, x_lims, y_lims, use_cuda=False):
+  """The reference's bilinear_interpolate, argument for argument (utils/sdf_utils.py:38): the signed distance d_obs (B,S,1) and its Jacobian J (B,S,2) at the points
+  stateb (B,S,2) of the grids imb -- (B,1,H,W) or (B,H,W), a TiledSdf, one grid or an expand()ed view shared by all rows.  Device tensors: ONE launch
+  (dgp_sdf_lookup; include/dgpmp2_hip.h states it) and one autograd node, once differentiable w.r.t. imb and stateb through one backward launch; a position view
+  th[:, :, :2] of a (B,n,d) trajectory tensor is read in place.  CPU tensors: bilinear_interpolate_torch.  `use_cuda` is unused: the tensors' device decides.
+  imb and stateb must share a floating dtype, which BOTH outputs take.  The one difference to the reference: for float32 inputs it returns d_obs as float64 (its
+  weights are DoubleTensors) and J as float32; here both are float32, computed in float64 and rounded once."""
+  if stateb.is_cuda:
+    from ..gpmp2.sdf_lookup import device_bilinear_interpolate
+    return device_bilinear_interpolate(imb, stateb, res, x_lims, y_lims)
+  return bilinear_interpolate_torch(imb, stateb, res, x_lims, y_lims)
+
+
+def sdf_lookup(imb, stateb, res, x_lims, y_lims, clearance):
+  """bilinear_interpolate with the collision summary of every row of points, in ONE launch on device tensors -> a LookupResult: d_obs (B,S,1), J (B,S,2), and the
+  (B,) columns solved (no point has d_obs <= clearance: check_solved's test), num_blocked, first_blocked (-1: none), min_dist, min_index; `raw` is the (B,5)
+  float64 tensor.  No autograd (inputs are detached); nothing is synchronised.  CPU tensors: the torch mirror and the same columns from torch ops."""
+  from ..gpmp2 import sdf_lookup as _sl
+  if stateb.is_cuda: return _sl.device_sdf_lookup(imb, stateb, res, x_lims, y_lims, clearance)
+  import torch
+  with torch.no_grad():
+    g = _rowmajor_grids(imb.detach()).to(torch.float64)
+    d64, _ = bilinear_interpolate_torch(g, stateb.detach().to(torch.float64), res, x_lims, y_lims)      # the summary reads the distance before it is rounded
+    d, J = bilinear_interpolate_torch(imb.detach(), stateb.detach(), res, x_lims, y_lims)
+    return _sl.LookupResult(d, J, _sl.summary_torch(d64, clearance))
+
+
 def rgb2gray(rgb):
   return np.dot(rgb[..., :3], [0.299, 0.587, 0.114])
 

@@ -586,6 +586,61 @@ int dgp_step_loss_backward(int32_t dtype, int32_t batch, int32_t num_states, int
                   void* g_unw_sg, void* g_unw_gp, void* g_unw_obs,                     /* (B) io dtype; each may be NULL */
                   void* stream);
 
+/* The reference's bilinear_interpolate (utils/sdf_utils.py:38-107) at arbitrary points of a batch, its gradient, and the per-row collision summary behind
+ * check_solved (learning/train_initializer.py:81-88).  No handle: the reference function takes res, x_lims and y_lims explicitly (check_solved passes a cell size
+ * taken from im_size, not from the padded width).  dtype (DGP_F32 / DGP_F64) is the type of every `void*` array below; B = batch, S = num_points.
+ * points  (B,S,>=2): x, y are the first two elements of a row; point_stride is the row pitch in elements (>= 2), the batch pitch is S * point_stride: a (B,n,d)
+ *   trajectory tensor is looked up at its positions with point_stride = d, without a copy.
+ * sdf     rows >= 1, cols >= 2 (a single column: DGP_EUNSUPPORTED), batch_stride (0 = one grid for every row), layout ROWMAJOR / TILED4.
+ * Arithmetic.  fp64 whatever dtype, FMA contraction off, every operation in the order written, left to right inside a pair of parentheses; `u / res` is the IEEE
+ *   quotient for finite u, the sign of a zero kept (a non-finite u gives NaN).  Every stored value is rounded once to dtype.
+ * Forward (sdf_utils.py:57-94; the in-limits rule of :96-106 is a no-op on torch >= 1.2 and MAX_D is never produced):
+ *   ox = 0 - x_lims[0] / res,  oy = 0 - y_lims[0] / res;   px = ox + x / res,  py = oy - y / res
+ *   x1 = floor(px), x2 = x1 + 1, y1 = floor(py), y2 = y1 + 1 as integers, THEN each clamped to [0, cols - 1] / [0, rows - 1].  floor(px) is saturated to +-1e9 before
+ *   the conversion and a NaN lands on an in-range index (the step kernels' index computation): for |px| >= 1e9 the index saturates -- after the clamp the same taps
+ *   as the exact integer would give, while the reference's own int64 cast is undefined there.
+ *   a, b, c, e = grid[y1][x1], grid[y1][x2], grid[y2][x1], grid[y2][x2]  (the reference's dx1y1, dx2y1, dx1y2, dx2y2), converted to double
+ *   wja = (double)y2 - py,  wjb = py - (double)y1,  wjc = (double)x2 - px,  wjd = px - (double)x1      (clamped integers against unclamped px, py)
+ *   wa = wjc * wja,  wb = wjd * wja,  wc = wjc * wjb,  wd = wjd * wjb
+ *   d  = ((wa * a + wb * b) + wc * c) + wd * e
+ *   J0 = (-1.0 * (wja * (b - a) + wjb * (e - c))) / res        J1 = (wjc * (c - a) + wjd * (e - b)) / res
+ * Outputs (each may be NULL, not all three): d_obs (B,S) and J (B,S,2) of dtype; summary (B, DGP_LOOKUP_COUNT) DOUBLES over the S points of a row, from the fp64 d
+ *   before rounding:  SOLVED 1.0 iff no point has d <= clearance (check_solved's test: a NaN does not block);  NUM_BLOCKED the count of d <= clearance;
+ *   FIRST_BLOCKED the smallest such index, -1.0 if none;  MIN_DIST the smallest d, a NaN wins (torch.min);  MIN_INDEX its index, the smallest among equals (of the
+ *   first NaN if any).  clearance is read by the summary only and must be finite when summary is given.
+ * Backward, cotangents g_d (B,S) and g_J (B,S,2) of dtype, either may be NULL (= 0), gd = g_d, g0 = g_J[0], g1 = g_J[1] converted to double:
+ *   cr   = (((e - c) - b) + a) / res
+ *   g_px = gd * (wja * (b - a) + wjb * (e - c)) + g1 * cr          g_points[0] =   g_px / res
+ *   g_py = gd * (wjc * (c - a) + wjd * (e - b)) - g0 * cr          g_points[1] = -(g_py / res)
+ *   t_a  = gd * (wjc * wja) + (g0 * wja - g1 * wjc) / res          t_b = gd * (wjd * wja) - (g0 * wja + g1 * wjd) / res
+ *   t_c  = gd * (wjc * wjb) + (g0 * wjb + g1 * wjc) / res          t_e = gd * (wjd * wjb) + (g1 * wjd - g0 * wjb) / res
+ *   g_points (B,S,2) dense, of dtype, WRITTEN.  g_sdf: t_a, t_b, t_c, t_e are ADDED to the cells of a, b, c, e with device-scope atomics (the caller zeroes it):
+ *   grids in sdf->layout, g_sdf_batch_stride elements apart (0 = one grid).  sdf->grad_mode DGP_GSDF_DENSE: cells of dtype, every contribution rounded once to dtype,
+ *   then added; DGP_GSDF_DENSE_F64: cells are doubles whatever dtype, contributions unrounded.  Clamped cells need no special case: coinciding taps receive both
+ *   contributions.  Floor and clamp are piecewise constant: no gradient passes through them, as in the reference's autograd.  Either output may be NULL, not both.
+ * Pointers need only be aligned to their element type: a point / J / g_points row moves as one 8-byte (fp32) or 16-byte (fp64) vector where point_stride == 2 and
+ * the pointers of the call allow it, element by element otherwise, the same bits either way.
+ * DGP_EINVAL, nothing launched: a bad dtype; batch or num_points < 1; NULL points, sdf, x_lims or y_lims; point_stride < 2; res not positive and finite; limits
+ * with hi <= lo; all outputs NULL; a summary without a finite clearance; backward without a cotangent; g_sdf_copies < 1.  DGP_EUNSUPPORTED: cols < 2;
+ * DGP_GSDF_SPARSE; g_sdf_copies > 1.  The forward uses no atomics: bit-identical from run to run.  Nothing allocated or synchronised: capturable in a HIP graph. */
+#define DGP_LOOKUP_SOLVED        0
+#define DGP_LOOKUP_NUM_BLOCKED   1
+#define DGP_LOOKUP_FIRST_BLOCKED 2
+#define DGP_LOOKUP_MIN_DIST      3
+#define DGP_LOOKUP_MIN_INDEX     4
+#define DGP_LOOKUP_COUNT         5
+int dgp_sdf_lookup(int32_t dtype, int32_t batch, int32_t num_points,
+                   const void* points, int64_t point_stride,
+                   const DgpSdf* sdf, double res, const double x_lims[2], const double y_lims[2],
+                   double clearance,                                                  /* summary only */
+                   void* d_obs, void* J, double* summary, void* stream);
+int dgp_sdf_lookup_backward(int32_t dtype, int32_t batch, int32_t num_points,
+                   const void* points, int64_t point_stride,
+                   const DgpSdf* sdf, double res, const double x_lims[2], const double y_lims[2],
+                   const void* g_d, const void* g_J,                                  /* either may be NULL (= 0) */
+                   void* g_points, void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies,
+                   void* stream);
+
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
  * hipExtLaunchKernelGGL does -- hipEventElapsedTime(start, stop) is then that kernel's execution time, the quantity
