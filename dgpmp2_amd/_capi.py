@@ -79,6 +79,11 @@ class DgpPathParams(C.Structure):
   _fields_ = [('clearance', C.c_double), ('max_sweeps', C.c_int32), ('path_cap', C.c_int32)]
 
 
+class DgpShortcutParams(C.Structure):
+  _fields_ = [('clearance', C.c_double), ('check_step', C.c_double), ('path_cap', C.c_int32), ('vertex_cap', C.c_int32), ('lookahead', C.c_int32),
+              ('reserved', C.c_int32)]
+
+
 class DgpLossWeights(C.Structure):
   _fields_ = [('vel_loss_lambda', C.c_double), ('ext_obs_lambda', C.c_double), ('ext_loss_weight', C.c_double)]
 
@@ -94,7 +99,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'shortcut_paths', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -162,6 +167,11 @@ class CApi(object):
     if self.init_paths is not None:
       self.init_paths.restype = C.c_int
       self.init_paths.argtypes = [vp, i32, C.POINTER(DgpSdf), vp, C.POINTER(DgpPathParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    # dgp_shortcut_paths: no twin in the emulator either
+    self.shortcut_paths = getattr(self.lib, prefix + 'shortcut_paths', None)
+    if self.shortcut_paths is not None:
+      self.shortcut_paths.restype = C.c_int
+      self.shortcut_paths.argtypes = [vp, i32, C.POINTER(DgpSdf), vp, C.POINTER(DgpShortcutParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     # dgp_gp_interpolate: no twin in the emulator either
     self.gp_interpolate = getattr(self.lib, prefix + 'gp_interpolate', None)
     if self.gp_interpolate is not None:
@@ -549,6 +559,21 @@ class Solver(object):
       raise NotImplementedError('%s does not export %sinit_paths (the CPU emulator has no twin of the path kernel)' % (self.api.path, self.api.prefix))
     self.api.check(self.api.init_paths(self.handle, batch, C.byref(sdf) if sdf is not None else None, env_index, C.byref(params) if params is not None else None,
                                        start, goal, th_init, field, path_cells, num_cells, length, info, stream))
+
+  @staticmethod
+  def shortcut_params(clearance, check_step, path_cap, vertex_cap=0, lookahead=1 << 30):
+    """DgpShortcutParams: a point is feasible where its bilinear distance exceeds `clearance`; check_step is the spacing of the check points of a segment (finite,
+    >= res / 16); path_cap / vertex_cap are the second dimensions of path_cells / vertex_index; lookahead bounds how far ahead of a vertex a shortcut is tried."""
+    return DgpShortcutParams(float(clearance), float(check_step), int(path_cap), int(vertex_cap), int(min(int(lookahead), 1 << 30)), 0)
+
+  def shortcut_paths(self, batch, sdf, params, start, goal, path_cells, num_cells, th, env_index=None, vertex_index=None, num_vertices=None, length=None, info=None,
+                     stream=None):
+    """dgp_shortcut_paths: th (B,n,4) of the I/O type, in-out, from start / goal (B,1,4) and the path_cells (B,path_cap) / num_cells (B) int32 dgp_init_paths wrote;
+    vertex_index (B,vertex_cap), num_vertices (B) and info (B) int32, length (B) float64; one launch."""
+    if self.api.shortcut_paths is None:
+      raise NotImplementedError('%s does not export %sshortcut_paths (the CPU emulator has no twin of the shortcut kernel)' % (self.api.path, self.api.prefix))
+    self.api.check(self.api.shortcut_paths(self.handle, batch, C.byref(sdf) if sdf is not None else None, env_index, C.byref(params) if params is not None else None,
+                                           start, goal, path_cells, num_cells, th, vertex_index, num_vertices, length, info, stream))
 
   def eval_errors_backward(self, batch, th, start, goal, sdf, covs, g_err_ext=None, g_unw_sg=None, g_unw_gp=None, g_unw_obs=None,
                            g_th=None, g_start=None, g_goal=None, g_sdf=None, g_sdf_batch_stride=0, g_eps=None, stream=None, g_sdf_copies=1):

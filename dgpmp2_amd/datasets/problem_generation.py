@@ -6,7 +6,9 @@ Python rejection loops, one Env2D.is_feasible call per candidate point; here eve
 csrc/problem_sampler.hip) with counter-based randomness: problem number p of a seed is the same problem whatever batch it is drawn in.  The images are an input, or
 made on the device as well (datasets/obstacle_maps.py, dgp_obstacle_maps: the reference's obst_generator.py): generate_dataset then starts from a seed.  RRT*
 itself (OMPL) and plotting are not part of this build; the role of the reference's --rrt_star_init -- an initial trajectory that is collision-free where the straight
-line is not -- is taken by init_paths (dgp_init_paths, csrc/init_paths.hip): the 5-7 shortest grid path through the free cells, resampled to n states.
+line is not -- is taken by init_paths (dgp_init_paths, csrc/init_paths.hip): the 5-7 shortest grid path through the free cells, resampled to n states, and
+shortcut_paths (dgp_shortcut_paths, csrc/shortcut_paths.hip): that path pulled tight by line of sight, the role of the simplifySolution() call RRTStar.plan makes
+(diff_gpmp2/ompl_rrtstar.py:36-41).
 """
 import numpy as np
 import torch
@@ -42,11 +44,11 @@ class PathInfo(object):
   """What dgp_init_paths reports per problem, device tensors: `flags` (B,) int32 of INFO_* bits, `num_cells` (B,) int32 (cells of the traced path; 0 for a fallback),
   `length` (B,) float64 (arc length of the polyline start -> cells -> goal; the straight distance for a fallback), `path_cells` (B,path_cap) int32 (r * W + c of
   the traced cells, -1 behind them) or None when path_cap is 0, `field` (B,H,W) int32 or None: the BITS of the uint32 cost-to-go field (5 per axis move, 7 per
-  diagonal; -1 = 0xffffffff: blocked or unreached) when it was asked for."""
-  __slots__ = ('flags', 'num_cells', 'length', 'path_cells', 'field')
+  diagonal; -1 = 0xffffffff: blocked or unreached) when it was asked for, `shortcut` the ShortcutInfo of init_paths(shortcut=True) or None."""
+  __slots__ = ('flags', 'num_cells', 'length', 'path_cells', 'field', 'shortcut')
 
-  def __init__(self, flags, num_cells, length, path_cells=None, field=None):
-    self.flags, self.num_cells, self.length, self.path_cells, self.field = flags, num_cells, length, path_cells, field
+  def __init__(self, flags, num_cells, length, path_cells=None, field=None, shortcut=None):
+    self.flags, self.num_cells, self.length, self.path_cells, self.field, self.shortcut = flags, num_cells, length, path_cells, field, shortcut
 
   @property
   def fell_back(self): return (self.flags & (INFO_START_BLOCKED | INFO_GOAL_BLOCKED | INFO_UNREACHABLE | INFO_UNCONVERGED)) != 0      # th_init is the straight line
@@ -58,11 +60,82 @@ class PathInfo(object):
   def unconverged(self): return (self.flags & INFO_UNCONVERGED) != 0
 
 
+SHORTCUT_NO_PATH, SHORTCUT_INPUT_TRUNCATED, SHORTCUT_VERTEX_TRUNCATED, SHORTCUT_UNVERIFIED = 1, 2, 4, 8      # bits of dgp_shortcut_paths' `info`
+INITS = ('straight', 'grid_path', 'shortcut_path')
+
+
+class ShortcutInfo(object):
+  """What dgp_shortcut_paths reports per problem, device tensors: `flags` (B,) int32 of SHORTCUT_* bits, `num_vertices` (B,) int32 (vertices of the new polyline, the
+  start and the goal included; 0 where nothing was simplified), `length` (B,) float64 (its arc length; -1 where nothing was simplified), `vertex_index`
+  (B,vertex_cap) int32 (the kept indices into start, traced cells, goal; -1 behind them) or None when vertex_cap is 0 -- SHORTCUT_VERTEX_TRUNCATED is then set for
+  every simplified problem and says nothing else."""
+  __slots__ = ('flags', 'num_vertices', 'length', 'vertex_index')
+
+  def __init__(self, flags, num_vertices, length, vertex_index=None):
+    self.flags, self.num_vertices, self.length, self.vertex_index = flags, num_vertices, length, vertex_index
+
+  @property
+  def simplified(self): return (self.flags & (SHORTCUT_NO_PATH | SHORTCUT_INPUT_TRUNCATED)) == 0      # the trajectory was rewritten
+
+  @property
+  def unverified(self): return (self.flags & SHORTCUT_UNVERIFIED) != 0      # a kept segment of adjacent vertices is not visible
+
+  @property
+  def input_truncated(self): return (self.flags & SHORTCUT_INPUT_TRUNCATED) != 0
+
+
 def _layer(planner_or_layer):
   return getattr(planner_or_layer, 'plan_layer', planner_or_layer)
 
 
-def init_paths(planner_or_layer, sdfb, startb, goalb, env_index=None, clearance=None, max_sweeps=64, path_cap=0, return_field=False, dtype=None):
+def _check_init(init):
+  if init not in INITS: raise ValueError("init must be 'straight', 'grid_path' or 'shortcut_path', got %r" % (init,))
+
+
+def shortcut_paths(planner_or_layer, sdfb, startb, goalb, th_initb, path_info, env_index=None, clearance=None, check_step=None, lookahead=None, vertex_cap=0):
+  """Line-of-sight shortcutting of the grid paths of init_paths, on the device, one launch: the traced path of every problem is pulled tight by one greedy pass --
+  from a vertex, go to the farthest later vertex that is visible from it -- and resampled to n states like the grid path was: the role of the simplifySolution()
+  call RRTStar.plan makes before interpolate() (diff_gpmp2/ompl_rrtstar.py:36-41).  include/dgpmp2_hip.h states the exact rule.
+  sdfb, startb, goalb, env_index: as for init_paths, and the same ones.  th_initb (B,n,4), path_info: what init_paths returned for them; path_info.path_cells is
+  required (init_paths(path_cap=...) large enough for the longest path: a truncated path is left as it is and flagged).
+  clearance: a point is feasible where the bilinear distance exceeds it; default sphere_radius + epsilon_dist, as init_paths.  check_step: the spacing of the check
+  points of a segment, default a quarter of a cell.  lookahead: how many vertices ahead a shortcut is tried, default no bound.  vertex_cap > 0 asks for the kept
+  indices.
+  With no flag but SHORTCUT_VERTEX_TRUNCATED the whole new polyline keeps a distance above clearance - check_step, and it is never longer than the grid path.
+  -> (thb (B,n,4): a new tensor, th_initb is not modified; info: ShortcutInfo), device tensors."""
+  layer = _layer(planner_or_layer)
+  if not torch.is_tensor(sdfb) or not sdfb.is_cuda:
+    raise RuntimeError('dgpmp2_amd.shortcut_paths: `sdfb` must be a CUDA/ROCm tensor; this build has no CPU path')
+  for name, t in (('startb', startb), ('goalb', goalb), ('th_initb', th_initb)):
+    if not torch.is_tensor(t) or not t.is_cuda: raise RuntimeError('dgpmp2_amd.shortcut_paths: `%s` must be a CUDA/ROCm tensor; this build has no CPU path' % name)
+  if sdfb.dim() == 6:
+    raise ValueError('dgpmp2_amd.shortcut_paths reads row-major grids, not 4 x 4 tiles (TiledSdf): pass utils.sdf_utils.untile_sdf(sdfb) or the row-major tensor')
+  if path_info is None or path_info.path_cells is None:
+    raise ValueError('dgpmp2_amd.shortcut_paths needs the traced cells: call init_paths(..., path_cap=...) and pass its PathInfo')
+  if sdfb.dim() == 3: sdfb = sdfb.unsqueeze(1)
+  dtype = th_initb.dtype
+  if clearance is None:
+    from ..gpmp2.plan_layer import _f
+    clearance = _f(layer.robot_model.get_sphere_radii()) + _f(layer.obs_params['epsilon_dist'])
+  if check_step is None:
+    from ..gpmp2.plan_layer import _f
+    x_lims = [_f(v) for v in layer.env_params['x_lims']]
+    check_step = (x_lims[1] - x_lims[0]) / int(sdfb.shape[-1]) / 4
+  cells = path_info.path_cells.contiguous()
+  sp = _capi.Solver.shortcut_params(clearance, check_step, int(cells.shape[1]), vertex_cap, (1 << 30) if lookahead is None else lookahead)
+  if env_index is not None:
+    env_index = env_index.to(torch.int32)
+    grids = int(sdfb.shape[0])
+    if not (grids == 1 or sdfb.stride(0) == 0) and env_index.is_cuda and not torch.cuda.is_current_stream_capturing():
+      lo, hi = torch.aminmax(env_index)
+      if int(lo) < 0 or int(hi) >= grids: raise ValueError('env_index must lie in [0, %d), got values in [%d, %d]' % (grids, int(lo), int(hi)))
+  thb = th_initb.detach().clone(memory_format=torch.contiguous_format)
+  vertex_index, num_vertices, length, flags = layer.shortcut_paths(sdfb, startb, goalb, thb, cells, path_info.num_cells.contiguous(), sp, dtype, env_index)
+  return thb, ShortcutInfo(flags, num_vertices, length, vertex_index if vertex_cap > 0 else None)
+
+
+def init_paths(planner_or_layer, sdfb, startb, goalb, env_index=None, clearance=None, max_sweeps=64, path_cap=0, return_field=False, dtype=None, shortcut=False,
+               check_step=None, lookahead=None):
   """Collision-free initial trajectories for a batch of problems, on the device: for every (start, goal) pair the 5-7 shortest path through the free cells of its
   grid, resampled to n states at equal arc length, with the constant velocities of the reference's path_to_traj_avg_vel -- the role of --rrt_star_init
   (generate_optimal_paths_gpmp2.py:95-110).  include/dgpmp2_hip.h states the exact rule.
@@ -72,6 +145,9 @@ def init_paths(planner_or_layer, sdfb, startb, goalb, env_index=None, clearance=
   distance field (a problem that needs more falls back and is flagged), path_cap > 0 asks for the traced cells, return_field for the (B,H,W) distance fields.
   Without return_field the batch runs in chunks whose uint32 fields stay at or below 1 GiB; a problem's result does not depend on its position or batch, so
   chunking changes nothing.  Problems that fall back (info.fell_back) get the straight line of sample_problems.
+  shortcut=True: the grid paths go through shortcut_paths (check_step, lookahead: its parameters, at the same clearance) and th_initb is ITS trajectory -- a short
+  any-angle polyline instead of the staircase; info.shortcut is its ShortcutInfo.  With path_cap == 0 the path is then traced with path_cap = min(H W, 4 (H + W))
+  (info.path_cells is returned); a problem that fell back, or whose path is longer than that, keeps what it has without shortcut.
   -> (th_initb (B,n,4), info: PathInfo), device tensors."""
   layer = _layer(planner_or_layer)
   if not torch.is_tensor(sdfb) or not sdfb.is_cuda:
@@ -85,6 +161,11 @@ def init_paths(planner_or_layer, sdfb, startb, goalb, env_index=None, clearance=
   if clearance is None:
     from ..gpmp2.plan_layer import _f
     clearance = _f(layer.robot_model.get_sphere_radii()) + _f(layer.obs_params['epsilon_dist'])
+  if shortcut:
+    if path_cap == 0: path_cap = min(int(sdfb.shape[-2]) * int(sdfb.shape[-1]), 4 * (int(sdfb.shape[-2]) + int(sdfb.shape[-1])))
+    th, info = init_paths(layer, sdfb, startb, goalb, env_index, clearance, max_sweeps, path_cap, return_field, dtype)
+    th, info.shortcut = shortcut_paths(layer, sdfb, startb, goalb, th, info, env_index, clearance, check_step, lookahead)
+    return th, info
   pp = _capi.Solver.path_params(clearance, max_sweeps, path_cap)
   grids, B = int(sdfb.shape[0]), int(startb.shape[0])
   shared = grids == 1 or sdfb.stride(0) == 0
@@ -116,8 +197,8 @@ def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, c
   number of grids (one small device -> host copy; not under HIP-graph capture, where the caller vouches for them).  clearance: a point is feasible where its signed
   distance exceeds it; default sphere_radius + epsilon_dist + 0.1 (generate_optimal_paths_gpmp2.py:124).  (seed, first_problem + b) determine problem b.
   diagonal (B,) integer device tensor: -1 random, 0..3 the corner-to-corner problem of :134-145.  dtype: of the outputs, default that of sdfb.
-  init: 'straight' (the straight lines of the launch itself) or 'grid_path': th_initb is init_paths' for the pairs just sampled, at its default clearance (row-major
-  grids only).
+  init: 'straight' (the straight lines of the launch itself), 'grid_path': th_initb is init_paths' for the pairs just sampled, at its default clearance (row-major
+  grids only), or 'shortcut_path': init_paths(shortcut=True), the grid path pulled tight by line of sight.
   **params: margin (0.5), min_dist_frac (0.6), near_tries (15), max_draws (4096), corner_inset (0.2) -- _capi.DgpSampleParams.
   -> (startb (B,1,4), goalb (B,1,4), th_initb (B,n,4), info: SampleInfo), device tensors."""
   layer = _layer(planner_or_layer)
@@ -138,9 +219,9 @@ def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, c
       lo, hi = torch.aminmax(env_index)
       if int(lo) < 0 or int(hi) >= grids: raise ValueError('env_index must lie in [0, %d), got values in [%d, %d]' % (grids, int(lo), int(hi)))
   if diagonal is not None: diagonal = diagonal.to(torch.int32)
-  if init not in ('straight', 'grid_path'): raise ValueError("init must be 'straight' or 'grid_path', got %r" % (init,))
+  _check_init(init)
   startb, goalb, th_initb, draws, info = layer.sample_problems(sdfb, B, sp, dtype, env_index, diagonal, seed, first_problem)
-  if init == 'grid_path': th_initb = init_paths(layer, sdfb, startb, goalb, env_index=env_index, dtype=dtype)[0]
+  if init != 'straight': th_initb = init_paths(layer, sdfb, startb, goalb, env_index=env_index, dtype=dtype, shortcut=init == 'shortcut_path')[0]
   return startb, goalb, th_initb, SampleInfo(info, draws)
 
 
@@ -152,8 +233,9 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
     1. sdf_2d_batch(images, padlen=0, res=cell_size)                              (generate_2d_dataset.py:211; cell_size = (x_max - x_min) / image width)
     2. sample_problems: probs_per_env problems per environment; with first_diagonal the first problem of every environment is one of the four diagonals, drawn
        from `seed`                                                                (generate_optimal_paths_gpmp2.py:126-148)
-    3. planner.forward on the initial trajectories: the straight lines (init='straight'), or init_paths' collision-free grid paths (init='grid_path': the
-       reference's --rrt_star_init switch, :95-110, :156-159; generate_2d_dataset.py:225-226)                                                   (:181-184)
+    3. planner.forward on the initial trajectories: the straight lines (init='straight'), init_paths' collision-free grid paths (init='grid_path': the
+       reference's --rrt_star_init switch, :95-110, :156-159; generate_2d_dataset.py:225-226), or those paths pulled tight by line of sight
+       (init='shortcut_path': init_paths(shortcut=True), the simplifySolution() of ompl_rrtstar.py:36-41)                                       (:181-184)
     4. trajectory_metrics(eps=0): in_coll of every planned trajectory             (generate_2d_dataset.py:247-252)
        check_inter > 0: the verdict is that of the GP-interpolated dense trajectory with check_inter states inside every interval, planner.interpolate(th_opt,
        check_inter, sdfb, eps=0).in_collision -- a trajectory whose support states straddle an obstacle is caught (the reference's 'total_check_step' /
@@ -163,7 +245,7 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
   trajectory in collision when require_collision_free is set (the reference drops an environment by exception, :247-265).  Written environments are numbered densely.
   **params go to sample_problems.  -> {'num_envs': written, 'kept': [input indices], 'dropped': {input index: reason}, 'start', 'goal', 'th_init', 'th_opt': device
   tensors of ALL E * probs_per_env problems (problem e * probs_per_env + j), 'info': SampleInfo, 'in_coll': (E * probs_per_env,) bool, 'path_info': the PathInfo of
-  init_paths (None with init='straight')}.  With images=None, 'kept' and
+  init_paths (None with init='straight'; with init='shortcut_path' its .shortcut is the ShortcutInfo)}.  With images=None, 'kept' and
   'dropped' count in the num_envs generated environments, E is the number of them that went through the chain, and 'images' (E,1,H,W), 'env_numbers' (their numbers
   among the generated ones) and 'obstacle_info' (ObstacleInfo of all num_envs) are returned as well."""
   from ..utils.sdf_utils import sdf_2d_batch
@@ -174,7 +256,7 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
     capped_h, over_h = oinfo.capped.cpu().numpy(), oinfo.overlapping.cpu().numpy()
     good = [e for e in range(int(num_envs)) if not (capped_h[e] or over_h[e])]
     sel = torch.tensor(good, dtype=torch.long, device=gen.device)
-    if init not in ('straight', 'grid_path'): raise ValueError("init must be 'straight' or 'grid_path', got %r" % (init,))
+    _check_init(init)
     r = {'num_envs': 0, 'kept': [], 'dropped': {}, 'path_info': None}
     if good:
       r = generate_dataset(root_dir, mode, gen[sel], planner, probs_per_env, seed=seed, first_diagonal=first_diagonal,
@@ -190,7 +272,7 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
     r.update(images=gen[sel], env_numbers=good, obstacle_info=oinfo)
     return r
   if not torch.is_tensor(images) or not images.is_cuda: raise RuntimeError('dgpmp2_amd.generate_dataset: `images` must be a CUDA/ROCm tensor; this build has no CPU path')
-  if init not in ('straight', 'grid_path'): raise ValueError("init must be 'straight' or 'grid_path', got %r" % (init,))
+  _check_init(init)
   layer = planner.plan_layer
   im = images[:, 0] if images.dim() == 4 else images
   E, H, W = im.shape
@@ -204,7 +286,7 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
   if first_diagonal: diagonal[::P] = torch.from_numpy(np.random.RandomState(seed).randint(0, 4, E).astype(np.int32)).to(im.device)
   startb, goalb, th_initb, info = sample_problems(layer, sdf, B, env_index=env_index, seed=seed, diagonal=diagonal, **params)
   path_info = None
-  if init == 'grid_path': th_initb, path_info = init_paths(layer, sdf, startb, goalb, env_index=env_index)
+  if init != 'straight': th_initb, path_info = init_paths(layer, sdf, startb, goalb, env_index=env_index, shortcut=init == 'shortcut_path')
   sdfb = sdf.index_select(0, env_index.long())      # one grid per problem, what forward() takes
   imb = (im > 0.75).to(sdf.dtype).unsqueeze(1).index_select(0, env_index.long())
   with torch.no_grad():

@@ -1312,6 +1312,54 @@ class PlanLayer(nn.Module):
             path_cells.data_ptr() if cap > 0 else None, num_cells.data_ptr(), length.data_ptr(), info.data_ptr(), _raw_stream(dev))
     return th_initb, field, path_cells, num_cells, length, info
 
+  def shortcut_paths(self, sdfb, startb, goalb, thb, path_cells, num_cells, params, dtype=torch.float64, env_index=None):
+    """Line-of-sight shortcutting of the grid paths of init_paths in ONE launch (dgp_shortcut_paths; datasets.problem_generation.shortcut_paths is the documented
+    front end and fills `params`, a _capi.DgpShortcutParams).  sdfb, startb, goalb, env_index as for init_paths; thb (B,n,4) of `dtype`, contiguous, REWRITTEN in
+    place for every simplified problem; path_cells (B,path_cap) and num_cells (B) int32 as init_paths returned them.
+    -> vertex_index (B,vertex_cap) int32, num_vertices (B) int32, length (B) float64, info (B) int32."""
+    if sdfb is None: raise ValueError('shortcut_paths needs the signed-distance grids (sdfb)')
+    _require_cuda(sdfb, 'sdfb')
+    if sdfb.dim() == 6: raise ValueError('shortcut_paths reads row-major grids: untile a TiledSdf first (utils.sdf_utils.untile_sdf)')
+    B, dev = int(startb.shape[0]), sdfb.get_device()
+    for name, t in (('startb', startb), ('goalb', goalb), ('thb', thb), ('path_cells', path_cells), ('num_cells', num_cells)):
+      _require_cuda(t, name)
+      if t.get_device() != dev: _same_device(dev, **{name: t})
+    for name, t in (('startb', startb), ('goalb', goalb)):
+      if tuple(t.shape) != (B, 1, 4): raise ValueError('%s must be (B,1,4), got %s' % (name, tuple(t.shape)))
+    cap, vcap = int(params.path_cap), int(params.vertex_cap)
+    if tuple(thb.shape) != (B, self.num_traj_states, 4) or thb.dtype is not dtype or not thb.is_contiguous():
+      raise ValueError('thb must be a contiguous (%d,%d,4) tensor of %s, got %s %s' % (B, self.num_traj_states, dtype, tuple(thb.shape), thb.dtype))
+    if tuple(path_cells.shape) != (B, cap) or path_cells.dtype is not torch.int32 or not path_cells.is_contiguous():
+      raise ValueError('path_cells must be a contiguous int32 tensor of shape (%d,%d) (params.path_cap columns), got %s %s' % (B, cap, path_cells.dtype, tuple(path_cells.shape)))
+    if tuple(num_cells.shape) != (B,) or num_cells.dtype is not torch.int32 or not num_cells.is_contiguous():
+      raise ValueError('num_cells must be a contiguous int32 tensor of shape (%d,), got %s %s' % (B, num_cells.dtype, tuple(num_cells.shape)))
+    solver = self._solvers.get(dtype) or self._solver(dtype)
+    grids = int(sdfb.shape[0])
+    shared = grids == 1 or sdfb.stride(0) == 0
+    if env_index is None and not shared and grids != B:
+      raise ValueError('sdfb has %d grids for %d problems: pass env_index (the grid of each problem)' % (grids, B))
+    sd = self._sdf_args(sdfb, dtype, B if (shared or env_index is None) else grids, dev)
+    ei = None
+    if env_index is not None:
+      _require_cuda(env_index, 'env_index')
+      if env_index.get_device() != dev: _same_device(dev, env_index=env_index)
+      if env_index.dtype is not torch.int32 or env_index.dim() != 1 or env_index.shape[0] != B:
+        raise ValueError('env_index must be an int32 tensor of shape (%d,), got %s %s' % (B, env_index.dtype, tuple(env_index.shape)))
+      ei = env_index.contiguous()
+    device = sdfb.device
+    st, go = startb.detach().to(dtype).contiguous(), goalb.detach().to(dtype).contiguous()
+    vertex_index = torch.empty((B, vcap), dtype=torch.int32, device=device)
+    num_vertices = torch.empty((B,), dtype=torch.int32, device=device)
+    info = torch.empty((B,), dtype=torch.int32, device=device)
+    length = torch.empty((B,), dtype=torch.float64, device=device)
+    import ctypes
+    api = _capi.get_api()
+    arg = _capi.DgpSdf(*sd[:7])
+    _launch(dev, api.shortcut_paths, solver.h, B, ctypes.byref(arg), _ptr(ei), ctypes.byref(params), st.data_ptr(), go.data_ptr(), path_cells.data_ptr(),
+            num_cells.data_ptr(), thb.data_ptr(), vertex_index.data_ptr() if vcap > 0 else None, num_vertices.data_ptr(), length.data_ptr(), info.data_ptr(),
+            _raw_stream(dev))
+    return vertex_index, num_vertices, length, info
+
 
 class TrajectoryMetrics(object):
   """Result of PlanLayer.trajectory_metrics: `raw` is the (B, DGP_METRIC_COUNT) float64 device tensor dgp_traj_metrics wrote (columns _capi.METRIC_NAMES),

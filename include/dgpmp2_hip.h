@@ -446,8 +446,8 @@ int dgp_obstacle_maps(const DgpHandle* h, int32_t batch, int32_t rows, int32_t c
  * RRT* run of 4 seconds per problem (init_planner.plan(start_conf, goal_conf, 4.0)), interpolate(num_states) and path_to_traj_avg_vel (utils/planner_utils.py:60-71).
  * RRT* is randomised and OMPL is not part of this build, so the PATH below has no counterpart in the reference and no fixture from it; what has one is the validity
  * rule -- RRTStar.isStateValid -> Env2D.is_feasible(state, sphere_radius + epsilon_dist) (diff_gpmp2/ompl_rrtstar.py:18, :48-50) -- and the velocities of
- * path_to_traj_avg_vel.  The rule stated here is exact: tests/paths_oracle.py restates it and the kernel is held against that bit for bit.  No shortcutting or
- * smoothing (OMPL's simplifySolution), no any-angle paths.
+ * path_to_traj_avg_vel.  The rule stated here is exact: tests/paths_oracle.py restates it and the kernel is held against that bit for bit.  The path is a
+ * grid path; dgp_shortcut_paths (below) turns it into a short any-angle polyline, the part of OMPL's simplifySolution that is built.  No smoothing.
  * dof == 2 handles only; x_lims, y_lims, n = num_states and total_time_sec come from the handle.  sdf: row-major grids of the handle's io_dtype, shared
  * (batch_stride 0) or one per sample, sides up to 2^12; DGP_SDF_TILED4 is refused with DGP_EINVAL (not implemented here: pass the row-major grid).  env_index as for
  * dgp_sample_problems.  With res = (x_max - x_min) / W, orig_x = 0 - x_min / res, orig_y = 0 - y_min / res and the pixel coordinates px = orig_x + x / res,
@@ -491,6 +491,60 @@ int dgp_init_paths(const DgpHandle* h, int32_t batch, const DgpSdf* sdf, const i
                    uint32_t* field,                                /* (B,H,W): workspace AND output, required */
                    int32_t* path_cells, int32_t* num_cells, double* length, int32_t* info,   /* each may be NULL */
                    void* stream);
+
+/* Line-of-sight shortcutting of the grid paths of dgp_init_paths, ONE launch: the step RRTStar.plan makes between its tree path and interpolate(num_states),
+ * self.ss.simplifySolution() (diff_gpmp2/ompl_rrtstar.py:36-41) -- the trajectory the reference's Gauss-Newton receives is a short any-angle polyline.  Here one
+ * greedy pass of string pulling over the vertices of the traced path; a segment is usable where OMPL's discrete motion check finds every check point valid by
+ * RRTStar.isStateValid -> Env2D.is_feasible.  The rule is exact: tests/shortcut_oracle.py restates it and the kernel is held against that bit for bit.  OMPL's
+ * randomised shortcutting, smoothing and B-splines stay out.
+ * dof == 2 handles only; grids, env_index, res, orig_x, orig_y as for dgp_init_paths.  Everything below is fp64 whatever io_dtype, FMA contraction off, operations
+ * in the order written.
+ * Vertices.  V_0 .. V_{L+1} are those of dgp_init_paths' "Trajectory" paragraph: V_0 the start point itself, V_1 .. V_L the points of the traced cells
+ *   path_cells[b][0 .. L-1], L = num_cells[b], x = (c - orig_x) * res, y = (orig_y - r) * res with r = cell / W, c = cell % W, V_{L+1} the goal point itself.
+ * Feasible point.  feasible(x, y) is Env2D.is_feasible(point, clearance) (env/env_2d.py:86-90, :119-175): the bilinear distance is > clearance.  The distance is
+ *   that of dgp_sample_problems bit for bit (tests/problems_oracle.signed_distance): clamped taps, the weights from the clamped indices, MAX_D = x_max - x_min for a
+ *   point outside the limits (closed on both sides), a NaN coordinate counting as outside.
+ * Visible segment.  OMPL's discrete motion check in the max-norm (no square root decides anything discrete): dx = Qx - Px, dy = Qy - Py,
+ *   m = fmax(fabs(dx), fabs(dy)) / check_step;  M = 1 if !(m > 1), else (int)ceil(m);  the check points are (Px + f * dx, Py + f * dy), f = (double)k / (double)M,
+ *   k = 0 .. M.  visible(P, Q) holds iff all M + 1 check points are feasible.  A segment with m > 2^20 is not visible (the bound of every loop over check points;
+ *   with check_step >= res / 16 and sides up to 2^12 no segment between points inside the limits comes near it).
+ * Greedy string pulling, one pass.  a = 0, index 0 is kept.  While a < L + 1: hi = min(L + 1, a + lookahead); j* is the largest j in [a + 2, hi] with
+ *   visible(V_a, V_j); if there is none, j* = a + 1, and that segment is kept whether or not it is visible -- if it is not, info bit 3 is set.  Keep j*, a = j*.
+ *   The kept indices 0 = k_0 < ... < k_{m-1} = L + 1 are the result.  visible is a pure predicate and "the largest j" is well defined: the result does not depend
+ *   on the order a kernel tests candidates or check points in.
+ * Trajectory.  The kept vertices go through the resampling rule of dgp_init_paths word for word: l_j, the serial arc lengths s_j and S over the kept vertices;
+ *   t = S * i / N, the lowest segment with s_{j+1} >= t, f = l_j > 0 ? (t - s_j) / l_j : 0; row N is the goal itself, S == 0 makes every row the start;
+ *   velocities (goal - start) / total_time_sec on every row; every value rounded once to io_dtype.
+ * Outputs.  th (B,n,4) io_dtype, in-out: the rows of a simplified problem are rewritten.  vertex_index (B, vertex_cap): the kept indices, -1 behind them.
+ *   num_vertices (B): m.  length (B): the new S.  info (B): bit 0 no path to simplify (num_cells <= 0: dgp_init_paths fell back); bit 1 the input was truncated
+ *   (num_cells > path_cap); bit 2 m > vertex_cap -- only vertex_index is truncated (so with vertex_cap == 0 it is set for every simplified problem, as bit 4 of
+ *   dgp_init_paths is with path_cap == 0); bit 3 at least one kept segment is not visible.  With bit 0 or 1 set th[b] is left untouched, num_vertices is 0,
+ *   vertex_index all -1 and length -1.0.  vertex_index, num_vertices, length and info may each be NULL.  A problem is a pure function of its grid, points, cells
+ *   and params: independent of batch size and position in the batch.
+ * What is guaranteed.  Every check point of a kept, visible segment is feasible.  The grid holds a distance transform, which changes by at most |dx| + |dy| between
+ *   two points, and so does its bilinear interpolant (a convex combination of four such values, whose weights move the value by at most the tap differences).
+ *   Consecutive check points are at most check_step apart in each coordinate, so any point of the segment lies within check_step / 2 of a check point in each
+ *   coordinate: its distance is above clearance - (check_step / 2 + check_step / 2).  With info bit 3 clear the whole polyline therefore has distance
+ *   > clearance - check_step.  The new length is <= the old one up to rounding: every kept segment replaces a run of the old polyline between the same two vertices
+ *   (triangle inequality).
+ * DGP_EINVAL, nothing launched: a NULL handle, params, sdf or grid, start, goal, path_cells, num_cells or th; dof != 2; batch < 1; a tiled or unknown layout, sides
+ * outside 1 .. 2^12, a negative batch stride; a NaN clearance; a check_step that is not finite or is < res / 16; path_cap outside 1 .. 2^18; vertex_cap < 0;
+ * lookahead < 1 (values above 2^30 count as 2^30); vertex_index non-NULL with vertex_cap == 0.
+ * One launch, no atomics, nothing allocated or synchronised: capturable in a HIP graph. */
+typedef struct DgpShortcutParams {
+  double  clearance;   /* a point is feasible where its bilinear distance is > clearance; reference: sphere_radius + epsilon_dist (ompl_rrtstar.py:18) */
+  double  check_step;  /* spacing of the check points of a segment in the max-norm, finite and >= res / 16 */
+  int32_t path_cap;    /* second dimension of path_cells, 1 .. 2^18 */
+  int32_t vertex_cap;  /* second dimension of vertex_index (>= 0) */
+  int32_t lookahead;   /* the farthest vertex tried from vertex a is a + lookahead (>= 1) */
+  int32_t reserved;    /* not read */
+} DgpShortcutParams;   /* 32 bytes */
+int dgp_shortcut_paths(const DgpHandle* h, int32_t batch, const DgpSdf* sdf, const int32_t* env_index, const DgpShortcutParams* p,
+                       const void* start, const void* goal,                        /* (B,1,4) io_dtype */
+                       const int32_t* path_cells, const int32_t* num_cells,        /* (B,path_cap), (B): what dgp_init_paths wrote */
+                       void* th,                                                   /* (B,n,4) io_dtype, in-out */
+                       int32_t* vertex_index, int32_t* num_vertices, double* length, int32_t* info,   /* each may be NULL */
+                       void* stream);
 
 /* GP-interpolated dense trajectories and the collision check BETWEEN support states, ONE launch.  The reference names the capability and never builds it:
  * gpmp2_planner.py:29-41 reads planner_params['total_check_step'] / ['use_gp_inter'], derives check_inter and sizes num_obs_factors for it, and no code interpolates.
