@@ -31,6 +31,7 @@ DENSE_NAMES = ('in_coll', 'num_colliding', 'avg_penetration', 'max_penetration',
 DGP_DENSE_IN_COLL, DGP_DENSE_NUM_COLLIDING, DGP_DENSE_AVG_PENETRATION, DGP_DENSE_MAX_PENETRATION, DGP_DENSE_FIRST_COLLIDING, DGP_DENSE_WORST_INDEX = range(6)
 DGP_DENSE_COUNT = len(DENSE_NAMES)
 DGP_MAX_NUM_INTER = 1023
+DGP_MAX_PRIOR_SAMPLES = 1 << 24      # dgp_prior_samples: the sample index shares a Philox counter word with the stream tag
 # entries of dgp_step_loss' (DGP_LOSS_COUNT) float64 terms (one_step_loss's return order) and columns of its (B, DGP_LOSS_PER_TRAJ) float64 per_traj
 LOSS_NAMES = ('total', 'pos', 'vel', 'cov', 'gp', 'sg', 'obs', 'ext')
 DGP_LOSS_TOTAL, DGP_LOSS_POS, DGP_LOSS_VEL, DGP_LOSS_COV, DGP_LOSS_GP, DGP_LOSS_SG, DGP_LOSS_OBS, DGP_LOSS_EXT = range(8)
@@ -99,7 +100,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'shortcut_paths', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'shortcut_paths', 'prior_samples', 'prior_launch_shape', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -172,6 +173,14 @@ class CApi(object):
     if self.shortcut_paths is not None:
       self.shortcut_paths.restype = C.c_int
       self.shortcut_paths.argtypes = [vp, i32, C.POINTER(DgpSdf), vp, C.POINTER(DgpShortcutParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    # dgp_prior_samples: no twin in the emulator either
+    self.prior_samples = getattr(self.lib, prefix + 'prior_samples', None)
+    self.prior_launch_shape = None
+    if self.prior_samples is not None:
+      self.prior_samples.restype = C.c_int
+      self.prior_samples.argtypes = [vp, i32, i32, vp, vp, vp, dbl, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
+      self.prior_launch_shape = f('prior_launch_shape'); self.prior_launch_shape.restype = C.c_int
+      self.prior_launch_shape.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     # dgp_gp_interpolate: no twin in the emulator either
     self.gp_interpolate = getattr(self.lib, prefix + 'gp_interpolate', None)
     if self.gp_interpolate is not None:
@@ -249,7 +258,7 @@ import sysconfig
 # never loaded by mistake
 PYCALL_PATH = os.path.join(_HERE, 'lib', '_dgp_pycall' + (sysconfig.get_config_var('EXT_SUFFIX') or '.so'))
 _PYCALL_ENTRIES = ('gn_step', 'gn_solve', 'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward',
-                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'traj_metrics', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward')
+                   'gn_step_errors', 'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'traj_metrics', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'prior_samples')
 
 
 def get_api():
@@ -321,6 +330,10 @@ class CtypesPycall(object):
     # (dtype, batch, num_points, points, point_stride, the seven DgpSdf fields, res, x_lo, x_hi, y_lo, y_hi, g_d, g_J, g_points, g_sdf, g_sdf_batch_stride, g_sdf_copies, stream)
     return self.api.sdf_lookup_backward(int(a[0]), int(a[1]), int(a[2]), a[3], int(a[4]), self._sdf(a, 5), float(a[12]), (C.c_double * 2)(float(a[13]), float(a[14])),
                                         (C.c_double * 2)(float(a[15]), float(a[16])), a[17], a[18], a[19], a[20], int(a[21]), int(a[22]), a[23])
+
+  def prior_samples(self, *a):
+    # (handle, batch, num_samples, start, goal, mean, scale, seed, first_problem, noise, th, noise_out, info, stream)
+    return self.api.prior_samples(a[0], int(a[1]), int(a[2]), a[3], a[4], a[5], float(a[6]), int(a[7]) & 0xffffffffffffffff, int(a[8]) & 0xffffffffffffffff, *a[9:])
 
 
 def get_pycall():
@@ -574,6 +587,22 @@ class Solver(object):
       raise NotImplementedError('%s does not export %sshortcut_paths (the CPU emulator has no twin of the shortcut kernel)' % (self.api.path, self.api.prefix))
     self.api.check(self.api.shortcut_paths(self.handle, batch, C.byref(sdf) if sdf is not None else None, env_index, C.byref(params) if params is not None else None,
                                            start, goal, path_cells, num_cells, th, vertex_index, num_vertices, length, info, stream))
+
+  def prior_samples(self, batch, num_samples, start, goal, th, mean=None, scale=1.0, seed=0, first_problem=0, noise=None, noise_out=None, info=None, stream=None):
+    """dgp_prior_samples: th (B,S,n,d) of the I/O type from start / goal (B,1,d) and mean (B,n,d) or None (the prior mean); noise / noise_out (B,S,n+1,d) float64 or
+    None (generated from seed and first_problem / not returned), info (B,S) int32 or None; one launch."""
+    if self.api.prior_samples is None:
+      raise NotImplementedError('%s does not export %sprior_samples (the CPU emulator has no twin of the sampling kernel)' % (self.api.path, self.api.prefix))
+    self.api.check(self.api.prior_samples(self.handle, int(batch), int(num_samples), start, goal, mean, float(scale), int(seed) & 0xffffffffffffffff, int(first_problem) & 0xffffffffffffffff, noise, th, noise_out,
+                                          info, stream))
+
+  def prior_launch_shape(self):
+    """(lanes per trajectory, 64-state blocks per trajectory) dgp_prior_samples launches for this handle: what its own dispatch reads."""
+    if self.api.prior_samples is None:
+      raise NotImplementedError('%s does not export %sprior_launch_shape (the CPU emulator has no twin of the sampling kernel)' % (self.api.path, self.api.prefix))
+    l, b = C.c_int32(), C.c_int32()
+    self.api.check(self.api.prior_launch_shape(self.handle, C.byref(l), C.byref(b)))
+    return l.value, b.value
 
   def eval_errors_backward(self, batch, th, start, goal, sdf, covs, g_err_ext=None, g_unw_sg=None, g_unw_gp=None, g_unw_obs=None,
                            g_th=None, g_start=None, g_goal=None, g_sdf=None, g_sdf_batch_stride=0, g_eps=None, stream=None, g_sdf_copies=1):

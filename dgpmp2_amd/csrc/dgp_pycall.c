@@ -53,6 +53,9 @@ static sdf_lookup_fn f_sdf_lookup;
 typedef int (*sdf_lookup_bwd_fn)(int32_t, int32_t, int32_t, const void*, int64_t, const DgpSdf*, double, const double*, const double*, const void*, const void*, void*, void*,
                                  int64_t, int32_t, void*);
 static sdf_lookup_bwd_fn f_sdf_lookup_bwd;
+typedef int (*prior_samples_fn)(const DgpHandle*, int32_t, int32_t, const void*, const void*, const void*, double, uint64_t, uint64_t, const double*, void*, double*, int32_t*,
+                                void*);
+static prior_samples_fn f_prior_samples;
 static square_covs_fn f_square_covs;
 static square_covs_bwd_fn f_square_covs_bwd;
 typedef int (*sum_partial_grids_fn)(const void*, int32_t, int32_t, int64_t, double, void*, int32_t, void*);
@@ -102,7 +105,7 @@ static inline int64_t as_i64(PyObject* o, int* bad) {
   const DgpSdf* sdfp = sdf.data ? &sdf : NULL
 
 static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
-  NEED(18, "bind");
+  NEED(19, "bind");
   f_gn_step = (gn_step_fn)P(0);
   f_gn_solve = (gn_solve_fn)P(1);
   f_eval_errors = (eval_errors_fn)P(2);
@@ -121,6 +124,7 @@ static PyObject* py_bind(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
   f_step_loss_bwd = (step_loss_bwd_fn)P(15);
   f_sdf_lookup = (sdf_lookup_fn)P(16);
   f_sdf_lookup_bwd = (sdf_lookup_bwd_fn)P(17);
+  f_prior_samples = (prior_samples_fn)P(18);
   if (bad) return NULL;
   Py_RETURN_NONE;
 }
@@ -404,9 +408,26 @@ static PyObject* py_sdf_lookup_bwd(PyObject* self, PyObject* const* a, Py_ssize_
   return PyLong_FromLong(f_sdf_lookup_bwd(dt, B, S, pts, ps, sdf.data ? &sdf : NULL, res, xl, yl, gd, gJ, gp, gs, gstride, copies, stream));
 }
 
+/* prior_samples(handle, batch, num_samples, start, goal, mean, scale, seed, first_problem, noise, th, noise_out, info, stream) */
+static PyObject* py_prior_samples(PyObject* self, PyObject* const* a, Py_ssize_t nargs) {
+  NEED(14, "prior_samples");
+  BOUND(f_prior_samples);
+  const DgpHandle* h = (const DgpHandle*)P(0);
+  const int32_t batch = (int32_t)I(1), S = (int32_t)I(2);
+  const void *start = P(3), *goal = P(4), *mean = P(5);
+  const double scale = PyFloat_AsDouble(a[6]);
+  if (scale == -1.0 && PyErr_Occurred()) return NULL;
+  const uint64_t seed = (uint64_t)PyLong_AsUnsignedLongLongMask(a[7]), first = (uint64_t)PyLong_AsUnsignedLongLongMask(a[8]);
+  if (PyErr_Occurred()) return NULL;
+  const void* noise = P(9);
+  void *th = P(10), *noise_out = P(11), *info = P(12), *stream = P(13);
+  if (bad) return NULL;
+  return PyLong_FromLong(f_prior_samples(h, batch, S, start, goal, mean, scale, seed, first, (const double*)noise, th, (double*)noise_out, (int32_t*)info, stream));
+}
+
 static PyMethodDef methods[] = {
     {"bind", (PyCFunction)(void (*)(void))py_bind, METH_FASTCALL,
-     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward, traj_metrics, gp_interpolate, step_loss, step_loss_backward, sdf_lookup, sdf_lookup_backward): "
+     "bind(gn_step, gn_solve, eval_errors, gn_step_backward, eval_errors_backward, gn_solve_traced, gn_solve_backward, gn_step_errors, gn_step_errors_backward, sum_partial_grids, square_covariances, square_covariances_backward, traj_metrics, gp_interpolate, step_loss, step_loss_backward, sdf_lookup, sdf_lookup_backward, prior_samples): "
      "addresses of the C-ABI entry points"},
     {"gn_solve_traced", (PyCFunction)(void (*)(void))py_gn_solve_traced, METH_FASTCALL, "dgp_gn_solve_traced"},
     {"gn_solve_backward", (PyCFunction)(void (*)(void))py_gn_solve_backward, METH_FASTCALL, "dgp_gn_solve_backward"},
@@ -421,6 +442,7 @@ static PyMethodDef methods[] = {
     {"step_loss_backward", (PyCFunction)(void (*)(void))py_step_loss_bwd, METH_FASTCALL, "dgp_step_loss_backward"},
     {"sdf_lookup", (PyCFunction)(void (*)(void))py_sdf_lookup, METH_FASTCALL, "dgp_sdf_lookup"},
     {"sdf_lookup_backward", (PyCFunction)(void (*)(void))py_sdf_lookup_bwd, METH_FASTCALL, "dgp_sdf_lookup_backward"},
+    {"prior_samples", (PyCFunction)(void (*)(void))py_prior_samples, METH_FASTCALL, "dgp_prior_samples"},
     {"gn_step", (PyCFunction)(void (*)(void))py_gn_step, METH_FASTCALL, "dgp_gn_step"},
     {"gn_solve", (PyCFunction)(void (*)(void))py_gn_solve, METH_FASTCALL, "dgp_gn_solve"},
     {"eval_errors", (PyCFunction)(void (*)(void))py_eval_errors, METH_FASTCALL, "dgp_eval_errors"},

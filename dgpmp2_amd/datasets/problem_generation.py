@@ -84,6 +84,42 @@ class ShortcutInfo(object):
   def input_truncated(self): return (self.flags & SHORTCUT_INPUT_TRUNCATED) != 0
 
 
+PRIOR_OUTSIDE_LIMITS, PRIOR_NON_FINITE = 1, 2      # bits of dgp_prior_samples' `info`
+
+
+class PriorSampleInfo(object):
+  """What dgp_prior_samples reports per sample, device tensors: `flags` (B,S) int32 of PRIOR_* bits, `noise` (B,S,n+1,d) float64: the standard normals the samples
+  were made from (row 0 the start, rows 1 .. n-1 the n - 1 intervals, row n the goal observation) when return_noise was set, else None -- feeding them back as
+  `noise` reproduces the samples bit for bit."""
+  __slots__ = ('flags', 'noise')
+
+  def __init__(self, flags, noise=None): self.flags, self.noise = flags, noise
+
+  @property
+  def outside_limits(self): return (self.flags & PRIOR_OUTSIDE_LIMITS) != 0      # a position of the sample leaves x_lims / y_lims (samples are not clamped)
+
+  @property
+  def non_finite(self): return (self.flags & PRIOR_NON_FINITE) != 0
+
+
+def prior_samples(planner_or_layer, startb, goalb, num_samples, seed=0, first_problem=0, mean=None, scale=1.0, noise=None, return_noise=False, dtype=None):
+  """Initial trajectories for a multi-start, on the device, one launch: num_samples trajectories per problem drawn from the GP prior the planner optimises under --
+  N(mu, Sigma) with Sigma^-1 the matrix of the GN step without obstacle (and non-holonomic / velocity-limit) factors and without reg, mu its solution: smooth
+  trajectories from startb to goalb that spread most in the middle.  Gauss-Newton on the hinge cost converges to the local minimum its one initial trajectory
+  selects, and the straight line and the grid path both lie on the symmetry axis of an obstacle on their way; a batch of samples does not.  include/dgpmp2_hip.h
+  states the exact construction.
+  startb, goalb (B,1,d) device tensors.  (seed, first_problem + b, s) determine sample s of problem b, whatever the batch it is drawn in.  mean (B,n,d): the
+  trajectory the samples spread around -- None: the prior mean; the th_init of init_paths / shortcut_paths: samples around the grid path.  scale >= 0 multiplies the
+  deviation from the mean (0 returns the mean).  noise (B,S,n+1,d) float64: standard normals to use instead of generated ones.  dtype: of the samples, default
+  startb's.  Samples are neither clamped nor rejected: info.outside_limits flags those that leave the limits.
+  -> (thb (B,S,n,d), info: PriorSampleInfo), device tensors; thb.flatten(0, 1) is what forward() takes."""
+  layer = _layer(planner_or_layer)
+  for name, t in (('startb', startb), ('goalb', goalb), ('mean', mean), ('noise', noise)):
+    if t is not None and (not torch.is_tensor(t) or not t.is_cuda): raise RuntimeError('dgpmp2_amd.prior_samples: `%s` must be a CUDA/ROCm tensor; this build has no CPU path' % name)
+  th, noise_out, flags = layer.prior_samples(startb, goalb, num_samples, dtype, mean, scale, seed, first_problem, noise, return_noise)
+  return th, PriorSampleInfo(flags, noise_out)
+
+
 def _layer(planner_or_layer):
   return getattr(planner_or_layer, 'plan_layer', planner_or_layer)
 

@@ -498,6 +498,13 @@ class DiffGPMP2Planner(nn.Module):
     torch.cuda.graph."""
     return self.plan_layer.interpolate(thb, num_inter, sdfb, eps, return_cost)
 
+  def sample_prior(self, startb, goalb, num_samples, **kw):
+    """num_samples trajectories per problem drawn from the GP prior the planner optimises under -- the start and goal priors and the constant-velocity GP factors,
+    without obstacles -- in one launch: the initial trajectories of a multi-start (datasets.problem_generation.prior_samples: seed, first_problem, mean, scale,
+    noise, return_noise, dtype) -> (thb (B,S,n,d), PriorSampleInfo).  Flatten to (B S, n, d), repeat start / goal / grids S times, forward(), and keep the best
+    collision-free sample per problem.  No autograd; usable inside graphed_iteration / torch.cuda.graph.  No counterpart in the reference."""
+    return self.plan_layer.sample_prior(startb, goalb, num_samples, **kw)
+
   def step_loss(self, dthetab, th_currb, th_optb, errors, weights=None):
     """The loss of one training iteration -- the reference's one_step_loss(dthetab, th_optb - th_currb, qc, obscov, *errors, ...) (learning/train_planner.py:75-120,
     :328) -- in two launches, its backward in one: -> plan_layer.LossTerms(total, pos, vel, cov, gp, sg, obs, ext), 0-d float64 device tensors of which `total` is

@@ -1360,6 +1360,47 @@ class PlanLayer(nn.Module):
             _raw_stream(dev))
     return vertex_index, num_vertices, length, info
 
+  def prior_samples(self, startb, goalb, num_samples, dtype=None, mean=None, scale=1.0, seed=0, first_problem=0, noise=None, return_noise=False):
+    """num_samples trajectories per problem from the GP prior between startb and goalb in ONE launch (dgp_prior_samples; datasets.problem_generation.prior_samples is
+    the documented front end).  startb / goalb (B,1,d); mean (B,n,d) or None: the prior mean; noise (B,S,n+1,d) float64 standard normals or None: generated on the
+    device from (seed, first_problem + b, s).  -> th (B,S,n,d) of `dtype` (default: startb's), the (B,S,n+1,d) float64 normals used (None unless return_noise),
+    info (B,S) int32: bit 0 a position outside the limits, bit 1 a non-finite value."""
+    _require_cuda(startb, 'startb')
+    B, S, d, n, dev = int(startb.shape[0]), int(num_samples), self.state_dim, self.num_traj_states, startb.get_device()
+    if dtype is None: dtype = startb.dtype
+    if S != num_samples or S < 1 or S > _capi.DGP_MAX_PRIOR_SAMPLES: raise ValueError('num_samples must be an integer in 1..2^24, got %r' % (num_samples,))
+    if not (float(scale) >= 0.0) or float(scale) == float('inf'): raise ValueError('scale must be finite and >= 0, got %r' % (scale,))
+    for name, t in (('startb', startb), ('goalb', goalb)):
+      _require_cuda(t, name)
+      if t.get_device() != dev: _same_device(dev, **{name: t})
+      if tuple(t.shape) != (B, 1, d): raise ValueError('%s must be (%d,1,%d), got %s' % (name, B, d, tuple(t.shape)))
+    solver = self._solvers.get(dtype) or self._solver(dtype)
+    st, go = startb.detach().to(dtype).contiguous(), goalb.detach().to(dtype).contiguous()
+    mn = None
+    if mean is not None:
+      _require_cuda(mean, 'mean')
+      if mean.get_device() != dev: _same_device(dev, mean=mean)
+      if tuple(mean.shape) != (B, n, d): raise ValueError('mean must be (%d,%d,%d), got %s' % (B, n, d, tuple(mean.shape)))
+      mn = mean.detach().to(dtype).contiguous()
+    nz = None
+    if noise is not None:
+      _require_cuda(noise, 'noise')
+      if noise.get_device() != dev: _same_device(dev, noise=noise)
+      if tuple(noise.shape) != (B, S, n + 1, d): raise ValueError('noise must be (%d,%d,%d,%d): n + 1 rows of d standard normals per sample, got %s' % (B, S, n + 1, d, tuple(noise.shape)))
+      nz = noise.detach().to(torch.float64).contiguous()
+    device = startb.device
+    th = torch.empty((B, S, n, d), dtype=dtype, device=device)
+    noise_out = torch.empty((B, S, n + 1, d), dtype=torch.float64, device=device) if return_noise else None
+    info = torch.empty((B, S), dtype=torch.int32, device=device)
+    _launch(dev, self._pc.prior_samples, solver.h, B, S, st.data_ptr(), go.data_ptr(), _ptr(mn), float(scale), int(seed), int(first_problem), _ptr(nz), th.data_ptr(),
+            _ptr(noise_out), info.data_ptr(), _raw_stream(dev))
+    return th, noise_out, info
+
+  def sample_prior(self, startb, goalb, num_samples, **kw):
+    """datasets.problem_generation.prior_samples(self, startb, goalb, num_samples, **kw): GP-prior trajectory samples for a multi-start -> (thb (B,S,n,d), PriorSampleInfo)."""
+    from ..datasets.problem_generation import prior_samples
+    return prior_samples(self, startb, goalb, num_samples, **kw)
+
 
 class TrajectoryMetrics(object):
   """Result of PlanLayer.trajectory_metrics: `raw` is the (B, DGP_METRIC_COUNT) float64 device tensor dgp_traj_metrics wrote (columns _capi.METRIC_NAMES),

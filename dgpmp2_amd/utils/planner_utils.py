@@ -115,3 +115,54 @@ def gp_interpolate_traj(trajb, total_time_sec, total_time_step, num_inter):
   out = torch.cat((pos, vel), dim=-1)                       # (B, n - 1, K1, d)
   out[:, :, 0] = trajb[:, :-1]                              # offset 0: the support state itself, no arithmetic
   return torch.cat((out.reshape(B, (n - 1) * K1, d), trajb[:, -1:]), dim=1)
+
+
+def gp_prior_samples_torch(startb, goalb, noise, total_time_sec, total_time_step, Q_c_inv, K_s, K_g, mean=None, scale=1.0):
+  """Trajectory samples from the GP prior between startb and goalb (B,1,d) from the standard normals noise (B,S,n+1,d) -> (B,S,n,d): the documented mirror of
+  dgp_prior_samples (include/dgpmp2_hip.h states the construction) as plain batched torch ops on any device, in noise's dtype.  The unconditioned
+  constant-velocity chain from the start prior (row 0 of the noise; rows 1 .. n-1 drive the intervals) as two cumulative sums, one noisy observation of its last
+  state (row n), and Matheron's rule: xi_k = x_k - W_k y has exactly the covariance (A^T K^-1 A)^-1 of the planner's start, goal and GP factors.  mean (B,n,d) or
+  None: the prior mean Phi(t_k) start + W_k (goal - Phi(T) start); scale multiplies xi.  DiffGPMP2Planner.sample_prior does the same in one launch, generating the
+  normals on the device; the kernel's sums associate differently, so the two agree to rounding, not bit for bit."""
+  B, S, n1, d = noise.shape
+  n, dof = n1 - 1, d // 2
+  if n != int(total_time_step) + 1: raise ValueError('noise has %d rows for total_time_step %d (n + 1 rows are needed)' % (n1, total_time_step))
+  dev, dt_ = noise.device, noise.dtype
+  f = lambda v: float(v.item()) if torch.is_tensor(v) else float(v)
+  ks, kg, T = f(K_s), f(K_g), f(total_time_sec)
+  dt = T * 1.0 / total_time_step * 1.0
+  qc = torch.linalg.inv(torch.as_tensor(Q_c_inv, dtype=torch.float64, device='cpu'))
+  lc = torch.linalg.cholesky(qc)
+  t = torch.arange(n, dtype=torch.float64) * dt                                     # (n,)
+  t_end = float(t[-1])
+  I = torch.eye(dof, dtype=torch.float64)
+
+  def P(tt):      # (..., d, d): K_s^2 Phi Phi^T + Q(t)
+    tt = tt.reshape(-1, 1, 1)
+    pp = ks * ks * (1.0 + tt * tt) * I + tt ** 3 / 3.0 * qc
+    pv = ks * ks * tt * I + tt ** 2 / 2.0 * qc
+    vv = ks * ks * I + tt * qc
+    return torch.cat((torch.cat((pp, pv), -1), torch.cat((pv, vv), -1)), -2)
+  Sinv = torch.linalg.inv(P(torch.tensor([t_end], dtype=torch.float64))[0] + kg * kg * torch.eye(d, dtype=torch.float64))
+  tau = (t_end - t).reshape(-1, 1, 1)
+  Z = torch.zeros(n, dof, dof, dtype=torch.float64)
+  phi_t = torch.cat((torch.cat((I.expand(n, dof, dof), Z), -1), torch.cat((tau * I, I.expand(n, dof, dof)), -1)), -2)      # Phi(t_end - t_k)^T
+  W = (P(t) @ phi_t @ Sinv).to(device=dev, dtype=dt_)                                # (n, d, d)
+  lc, t = lc.to(device=dev, dtype=dt_), t.to(device=dev, dtype=dt_)
+  z0, zi, zg = noise[:, :, 0], noise[:, :, 1:n], noise[:, :, n]
+  lu, lw = zi[..., :dof] @ lc.T, zi[..., dof:] @ lc.T                                # (B,S,n-1,dof)
+  wp = (dt ** 1.5 / 3.0 ** 0.5) * lu
+  wv = (3.0 ** 0.5 / 2.0 * dt ** 0.5) * lu + (dt ** 0.5 / 2.0) * lw
+  v = torch.cumsum(torch.cat((ks * z0[..., None, dof:], wv), 2), 2)                  # (B,S,n,dof)
+  p = torch.cumsum(torch.cat((ks * z0[..., None, :dof], wp + dt * v[:, :, :-1]), 2), 2)
+  x = torch.cat((p, v), -1)
+  y = x[:, :, -1] + kg * zg                                                          # (B,S,d)
+  xi = x - torch.einsum('kij,bsj->bski', W, y)
+  if mean is None:
+    st, go = startb[:, 0].to(dt_), goalb[:, 0].to(dt_)
+    sp, sv = st[:, :dof], st[:, dof:]
+    r0 = torch.cat((go[:, :dof] - (sp + t_end * sv), go[:, dof:] - sv), -1)
+    m = torch.cat((sp[:, None] + t[None, :, None] * sv[:, None], sv[:, None].expand(B, n, dof)), -1) + torch.einsum('kij,bj->bki', W, r0)
+  else:
+    m = mean.to(dt_)
+  return m[:, None] + scale * xi

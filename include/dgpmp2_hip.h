@@ -695,6 +695,74 @@ int dgp_sdf_lookup_backward(int32_t dtype, int32_t batch, int32_t num_points,
                    void* g_points, void* g_sdf, int64_t g_sdf_batch_stride, int32_t g_sdf_copies,
                    void* stream);
 
+/* Trajectory samples from the GP prior, ONE launch: num_samples trajectories per problem drawn from N(mu, Sigma), the initial trajectories of a multi-start.  No
+ * counterpart in the reference, which gives Gauss-Newton one initial trajectory per problem.  Sigma^-1 = A^T K^-1 A is the matrix dgp_gn_step assembles from the start
+ * prior, the n - 1 GP factors and the goal prior alone (obstacle, non-holonomic and velocity-limit rows left out, no reg), mu that system's solution; only the static
+ * covariances of the handle enter (Q_c_inv, K_s, K_g -- no DgpCovs).  Every handle is accepted (every num_states, dof 2 and 3, both flags); the heading column of the
+ * dof 3 robot is a column like any other (as for dgp_gp_interpolate).
+ * Symbols.  d = 2 dof, n = num_states, dt the handle's (total_time_sec * 1.0 / (n - 1) * 1.0), t_k = (double)k * dt, t_end = t_(n-1); Phi(t) = [[I, t I], [0, I]];
+ *   Q_c = (Q_c_inv)^-1, L_c its lower Cholesky factor; Q(t) = [[t^3/3 Q_c, t^2/2 Q_c], [t^2/2 Q_c, t Q_c]];
+ *   P(t) = K_s^2 Phi(t) Phi(t)^T + Q(t): the covariance of the unconditioned chain at time t;  S = P(t_end) + K_g^2 I;  W(t) = P(t) Phi(t_end - t)^T S^-1.
+ * Construction, per problem b and sample s, from standard normals z laid out (n + 1, d): row 0 is z_0, row k + 1 = [u_k | u'_k] (dof entries each, k = 0 .. n - 2),
+ *   row n is z_g.
+ *   1. chain:  x_0 = K_s z_0;  x_(k+1) = Phi(dt) x_k + w_k,  w_k = [cp L_c u_k | cv1 L_c u_k + cv2 L_c u'_k],  cp = dt^(3/2) / sqrt 3, cv1 = (sqrt 3 / 2) sqrt dt,
+ *      cv2 = sqrt dt / 2  (Cov w_k = Q(dt));
+ *   2. noisy goal observation:  y = x_(n-1) + K_g z_g;
+ *   3. Matheron's rule:  xi_k = x_k - W(t_k) y  -- the chain conditioned on observing 0 at the goal: xi ~ N(0, Sigma) exactly;
+ *   4. th[b, s, k] = m_k + scale * xi_k,  m = mean[b] (n, d) where given, else m_k = mu_k = Phi(t_k) start + W(t_k) (goal - Phi(t_end) start).
+ *   mean may be any trajectory (the th_init of dgp_init_paths / dgp_shortcut_paths: samples around the grid path); scale >= 0 scales the spread, 0 returns m.
+ * Arithmetic.  fp64 whatever io_dtype, FMA contraction off, every operation in the order written, left to right inside a pair of parentheses; a product of a matrix
+ *   and a vector sums each row left to right, (M x)_i = (..(M_i0 x_0 + M_i1 x_1) + ..), a triangular one over its non-zero entries.  Stored values are rounded once.
+ *   Host constants (double, passed by value):
+ *     Cholesky of an N x N matrix A (lower triangle read), j = 0 .. N - 1:  s = A_jj, then s = s - G_jk G_jk for k = 0 .. j - 1;  G_jj = sqrt s  (s must be positive and
+ *       finite);  for i > j:  r = A_ij, then r = r - G_ik G_jk for k < j;  G_ij = r / G_jj.
+ *     Inverse of SPD A:  G as above;  V = G^-1:  V_jj = 1 / G_jj,  for i > j:  s = G_ij V_jj, then s = s + G_ik V_kj for k = j + 1 .. i - 1;  V_ij = (-s) / G_ii;
+ *       (A^-1)_ij for j <= i:  s = V_ii V_ij, then s = s + V_ki V_kj for k = i + 1 .. N - 1;  mirrored.
+ *     Q_c = inverse of Q_c_inv (which must be exactly symmetric), L_c = Cholesky of Q_c;  ks2 = K_s * K_s, kg2 = K_g * K_g;  sdt = sqrt dt, s3 = sqrt 3.0:
+ *       cp = (dt * sdt) / s3,  cv1 = (s3 / 2) * sdt,  cv2 = sdt / 2;  t_end = (double)(n - 1) * dt.
+ *     coefficients of P(t):  t2 = t * t, t3 = t2 * t;  i_pp = ks2 * (1 + t2), i_pv = ks2 * t, q_pp = t3 / 3, q_pv = t2 / 2, q_vv = t.
+ *     S at t = t_end, e = 1 on the diagonal of a dof x dof block and 0 off it, q = Q_c[i][j]:  S_pp = (i_pp + kg2) * e + q_pp * q,  S_pv = S_vp^T = i_pv * e + q_pv * q,
+ *       S_vv = (ks2 + kg2) * e + q_vv * q;  S^-1 by the inverse above (N = d).
+ *   Per trajectory, c a dof component, z_k row k of the normals, lu_k = L_c z_k[0 : dof], lw_k = L_c z_k[dof : d]:
+ *     velocity elements  ev_0 = K_s * z_0[dof + c],  ev_k = cv1 * lu_k[c] + cv2 * lw_k[c]  (k >= 1);        v = SCAN(ev)
+ *     position elements  ep_0 = K_s * z_0[c],        ep_k = cp * lu_k[c] + dt * v_(k-1)[c]  (k >= 1);        p = SCAN(ep);      x_k = [p_k | v_k]
+ *     SCAN, the inclusive prefix sum in this association order, a function of the index alone: inside each block of 64 consecutive indices starting at a multiple of
+ *       64, for off = 1, 2, 4, 8, 16, 32 in turn and for all i of the block with i % 64 >= off at once, e_i <- e_(i - off) + e_i; then, block after block from the
+ *       second on, e_i <- c + e_i for every i of the block, c the finished value of the last index of the block before.
+ *     y[c] = p_(n-1)[c] + K_g * z_g[c],  y[dof + c] = v_(n-1)[c] + K_g * z_g[dof + c];  g = S^-1 y.
+ *     W(t) g for a vector g, tau = t_end - t, the coefficients of P(t) as above:  hp = g[0 : dof],  hv[c] = tau * g[c] + g[dof + c];
+ *       ap[c] = q_pp * hp[c] + q_pv * hv[c],  av[c] = q_pv * hp[c] + q_vv * hv[c];
+ *       (W g)[c] = (i_pp * hp[c] + i_pv * hv[c]) + (Q_c ap)[c],   (W g)[dof + c] = (i_pv * hp[c] + ks2 * hv[c]) + (Q_c av)[c].
+ *     mu_k (mean == NULL), sp / sv the position / velocity part of start:  r0[c] = goal[c] - (sp[c] + t_end * sv[c]),  r0[dof + c] = goal[dof + c] - sv[c];  gr = S^-1 r0;
+ *       mu_k[c] = (sp[c] + t_k * sv[c]) + (W(t_k) gr)[c],   mu_k[dof + c] = sv[c] + (W(t_k) gr)[dof + c].
+ *     th[b, s, k][j] = m_k[j] + scale * (x_k[j] - (W(t_k) g)[j]).
+ *   Nothing here depends on the lanes per trajectory, the batch size or the position in the batch: th[b, s] is a pure function of (seed, first_problem + b, s), the
+ *   handle and start / goal / mean[b] -- or of noise[b, s] in their place.
+ * Noise.  noise (B, S, n + 1, d) DOUBLES, or NULL: generated -- Philox4x32-10 with the key of dgp_sample_problems (seed & 0xffffffff, seed >> 32) and counter
+ *   (problem lo, problem hi, j, (0x50 << 24) | s), problem = first_problem + b; num_samples <= 2^24, and 0x50 in the top byte of the last counter word is a stream no
+ *   other entry point uses.  Block j yields entries 2 j and 2 j + 1 of the trajectory's row-major (n + 1, d) array: u0, u1 from the four words as for
+ *   dgp_sample_problems (53 bits, [0, 1)),  r = sqrt(-2.0 * log(1.0 - u0)),  a = 6.283185307179586 * u1,  entries r * cos(a) and r * sin(a), the fp64 library functions
+ *   (a few ulp from the correctly rounded values: the generated normals are reproducible to 1e-13, not bit for bit, against another library; th from SUPPLIED noise is).
+ *   noise_out (B, S, n + 1, d) doubles or NULL: the normals used (a copy of noise where that is given): feeding it back as noise reproduces th bit for bit.
+ * info (B, S) int32 or NULL: bit 0 a stored position (the first two columns of a state) lies outside the handle's closed limits [x_min, x_max] x [y_min, y_max] (a NaN
+ *   is outside) -- samples are neither clamped nor rejected; bit 1 a stored value is not finite.
+ * start, goal (B,1,d) and mean (B,n,d) of io_dtype; th (B,S,n,d) io_dtype.  Pointers need only be aligned to their element type (th moves as 8- / 16-byte vectors where
+ * its address allows, the same bits either way).
+ * DGP_EINVAL, nothing launched: a NULL handle, start, goal or th; batch < 1; num_samples outside 1 .. 2^24, or batch * num_samples >= 2^31; scale negative or not
+ * finite; Q_c_inv not symmetric positive definite.  One launch, no atomics, nothing allocated, copied or synchronised: capturable in a HIP graph. */
+int dgp_prior_samples(const DgpHandle* h, int32_t batch, int32_t num_samples,
+                      const void* start, const void* goal,      /* (B,1,d) io_dtype */
+                      const void* mean,                         /* (B,n,d) io_dtype or NULL = mu */
+                      double scale, uint64_t seed, uint64_t first_problem,
+                      const double* noise,                      /* (B,S,n+1,d) doubles or NULL = generate */
+                      void* th,                                 /* (B,S,n,d) io_dtype */
+                      double* noise_out,                        /* (B,S,n+1,d) doubles or NULL */
+                      int32_t* info,                            /* (B,S) or NULL */
+                      void* stream);
+/* What dgp_prior_samples launches for this handle (the function its dispatch itself reads): lanes per trajectory (16 / 32 / 64, from num_states) and the number of
+ * 64-state blocks a wavefront walks (1: one pass; more: the block loop, two passes).  Either pointer may be NULL.  No effect on any result. */
+int dgp_prior_launch_shape(const DgpHandle* h, int32_t* lanes_per_traj, int32_t* blocks);
+
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
  * hipExtLaunchKernelGGL does -- hipEventElapsedTime(start, stop) is then that kernel's execution time, the quantity
