@@ -31,6 +31,9 @@ DENSE_NAMES = ('in_coll', 'num_colliding', 'avg_penetration', 'max_penetration',
 DGP_DENSE_IN_COLL, DGP_DENSE_NUM_COLLIDING, DGP_DENSE_AVG_PENETRATION, DGP_DENSE_MAX_PENETRATION, DGP_DENSE_FIRST_COLLIDING, DGP_DENSE_WORST_INDEX = range(6)
 DGP_DENSE_COUNT = len(DENSE_NAMES)
 DGP_MAX_NUM_INTER = 1023
+DGP_HEADING_LINEAR, DGP_HEADING_TANGENT = 0, 1      # dgp_heading_lift: DgpHeadingParams.heading_mode
+DGP_END_SUPPLIED, DGP_END_TANGENT, DGP_END_RANDOM = 0, 1, 2      # ... start_end / goal_end
+DGP_VEL_KEEP, DGP_VEL_DIFF = 0, 1      # ... velocity_mode
 DGP_MAX_PRIOR_SAMPLES = 1 << 24      # dgp_prior_samples: the sample index shares a Philox counter word with the stream tag
 # entries of dgp_step_loss' (DGP_LOSS_COUNT) float64 terms (one_step_loss's return order) and columns of its (B, DGP_LOSS_PER_TRAJ) float64 per_traj
 LOSS_NAMES = ('total', 'pos', 'vel', 'cov', 'gp', 'sg', 'obs', 'ext')
@@ -85,6 +88,11 @@ class DgpShortcutParams(C.Structure):
               ('reserved', C.c_int32)]
 
 
+class DgpHeadingParams(C.Structure):
+  _fields_ = [('heading_mode', C.c_int32), ('start_end', C.c_int32), ('goal_end', C.c_int32), ('velocity_mode', C.c_int32), ('blend', C.c_int32), ('reserved', C.c_int32),
+              ('seed', C.c_uint64), ('first_problem', C.c_uint64)]
+
+
 class DgpLossWeights(C.Structure):
   _fields_ = [('vel_loss_lambda', C.c_double), ('ext_obs_lambda', C.c_double), ('ext_loss_weight', C.c_double)]
 
@@ -100,7 +108,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'shortcut_paths', 'prior_samples', 'prior_launch_shape', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'shortcut_paths', 'prior_samples', 'prior_launch_shape', 'heading_lift', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -181,6 +189,11 @@ class CApi(object):
       self.prior_samples.argtypes = [vp, i32, i32, vp, vp, vp, dbl, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
       self.prior_launch_shape = f('prior_launch_shape'); self.prior_launch_shape.restype = C.c_int
       self.prior_launch_shape.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    # dgp_heading_lift: no twin in the emulator either
+    self.heading_lift = getattr(self.lib, prefix + 'heading_lift', None)
+    if self.heading_lift is not None:
+      self.heading_lift.restype = C.c_int
+      self.heading_lift.argtypes = [vp, i32, C.POINTER(DgpHeadingParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     # dgp_gp_interpolate: no twin in the emulator either
     self.gp_interpolate = getattr(self.lib, prefix + 'gp_interpolate', None)
     if self.gp_interpolate is not None:
@@ -603,6 +616,20 @@ class Solver(object):
     l, b = C.c_int32(), C.c_int32()
     self.api.check(self.api.prior_launch_shape(self.handle, C.byref(l), C.byref(b)))
     return l.value, b.value
+
+  @staticmethod
+  def heading_params(heading_mode=DGP_HEADING_TANGENT, start_end=DGP_END_SUPPLIED, goal_end=DGP_END_SUPPLIED, velocity_mode=DGP_VEL_DIFF, blend=1, seed=0, first_problem=0):
+    """DgpHeadingParams: how dgp_heading_lift forms the headings (tangent / the reference's linear rule), each end heading (supplied / the path's own tangent /
+    random from (seed, first_problem + b)) and the velocities (finite differences / kept), and over how many rows an end's heading error is blended out (1 .. n - 1)."""
+    return DgpHeadingParams(int(heading_mode), int(start_end), int(goal_end), int(velocity_mode), int(blend), 0, int(seed) & 0xffffffffffffffff, int(first_problem) & 0xffffffffffffffff)
+
+  def heading_lift(self, batch, params, th2, start, goal, th, start_heading=None, goal_heading=None, turns_in=None, turns_out=None, info=None, stream=None):
+    """dgp_heading_lift (a dof 3 handle): start / goal (B,1,6) and th (B,n,6) of the I/O type from the planar th2 (B,n,4); start_heading / goal_heading (B) and
+    turns_in / turns_out (B,n) float64 or None, info (B) int32 or None; one launch."""
+    if self.api.heading_lift is None:
+      raise NotImplementedError('%s does not export %sheading_lift (the CPU emulator has no twin of the lift kernel)' % (self.api.path, self.api.prefix))
+    self.api.check(self.api.heading_lift(self.handle, int(batch), C.byref(params) if params is not None else None, th2, start_heading, goal_heading, turns_in, start, goal, th,
+                                         turns_out, info, stream))
 
   def eval_errors_backward(self, batch, th, start, goal, sdf, covs, g_err_ext=None, g_unw_sg=None, g_unw_gp=None, g_unw_obs=None,
                            g_th=None, g_start=None, g_goal=None, g_sdf=None, g_sdf_batch_stride=0, g_eps=None, stream=None, g_sdf_copies=1):

@@ -505,6 +505,14 @@ class DiffGPMP2Planner(nn.Module):
     collision-free sample per problem.  No autograd; usable inside graphed_iteration / torch.cuda.graph.  No counterpart in the reference."""
     return self.plan_layer.sample_prior(startb, goalb, num_samples, **kw)
 
+  def lift_headings(self, th2b, **kw):
+    """A planar trajectory (B,n,4) -- a straight line, init_paths' grid path, its shortcut -- lifted to a problem of the non-holonomic x-y-heading robot in one
+    launch: the heading follows the path's tangent, unwrapped, blended into the end headings; the velocities are the path's own central differences
+    (datasets.problem_generation.lift_headings: start_heading, goal_heading, heading, ends, velocity, blend, seed, first_problem, turns, return_turns)
+    -> (startb, goalb (B,1,6), thb (B,n,6), HeadingInfo).  A dof 3 planner only.  No autograd; usable inside torch.cuda.graph.  The reference builds only
+    straight_line_trajb for this robot: heading='linear', velocity='keep'."""
+    return self.plan_layer.lift_headings(th2b, **kw)
+
   def step_loss(self, dthetab, th_currb, th_optb, errors, weights=None):
     """The loss of one training iteration -- the reference's one_step_loss(dthetab, th_optb - th_currb, qc, obscov, *errors, ...) (learning/train_planner.py:75-120,
     :328) -- in two launches, its backward in one: -> plan_layer.LossTerms(total, pos, vel, cov, gp, sg, obs, ext), 0-d float64 device tensors of which `total` is

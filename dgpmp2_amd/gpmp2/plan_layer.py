@@ -756,6 +756,7 @@ class PlanLayer(nn.Module):
     self.last_info = None
     self._last = None
     self._solvers = {}                 # torch dtype -> _capi.Solver
+    self._planar = {}                  # torch dtype -> the planar companion _capi.Solver of a dof 3 layer (_planar_solver)
     self._sdf_cache = None             # marshalled arguments of the last SDF tensor seen (see _sdf_args)
     self._err_protos = {}              # (B, dtype, device index) -> (B,1,1) prototype for torch.empty_like
     self._info_bufs = {}               # (B, device index, raw stream) -> the int32 flag buffer launches on that stream write
@@ -783,6 +784,22 @@ class PlanLayer(nn.Module):
       s = _capi.Solver(cfg)
       assert s.M == self.M
       self._solvers[dtype] = s
+    return s
+
+  def _planar_solver(self, dtype):
+    """The handle the planar side kernels (dgp_sample_problems, dgp_init_paths, dgp_shortcut_paths: dof 2 only) run on.  A dof 2 layer: its own.  The x-y-heading
+    robot (dof 3): a planar COMPANION handle, built once per dtype and kept -- the same num_states, I/O type, total_time_sec, limits, sphere_radius, epsilon_dist,
+    cost_sigma, K_s, K_g and reg, the top-left 2 x 2 of Q_c_inv, no flags; what those kernels return goes through lift_headings."""
+    if self.dof == 2: return self._solvers.get(dtype) or self._solver(dtype)
+    s = self._planar.get(dtype)
+    if s is None:
+      gp, ob = self.gp_params, self.obs_params
+      cfg = _capi.make_config(
+          num_states=self.num_traj_states, dof=2, io_dtype=_io_code(dtype), total_time_sec=_f(self.total_time_sec),
+          x_lims=[_f(v) for v in self.env_params['x_lims']], y_lims=[_f(v) for v in self.env_params['y_lims']],
+          K_s=_f(gp['K_s']), K_g=_f(gp['K_g']), reg=_f(self.optim_params['reg']), sphere_radius=_f(self.robot_model.get_sphere_radii()),
+          Q_c_inv=[row[:2] for row in self._qc_rows[:2]], cost_sigma=_f(ob['cost_sigma']), epsilon_dist=_f(ob['epsilon_dist']), nlinks=self.nlinks)
+      s = self._planar[dtype] = _capi.Solver(cfg)
     return s
 
   def _err_proto(self, B, dtype, dev, like):
@@ -1237,7 +1254,7 @@ class PlanLayer(nn.Module):
     if sdfb is None: raise ValueError('sample_problems needs the signed-distance grids (sdfb)')
     _require_cuda(sdfb, 'sdfb')
     B, dev = int(num_problems), sdfb.get_device()
-    solver = self._solvers.get(dtype) or self._solver(dtype)
+    solver = self._planar_solver(dtype)
     grids = int(sdfb.shape[0])
     shared = grids == 1 or sdfb.stride(0) == 0
     if env_index is None and not shared and grids != B:
@@ -1280,7 +1297,7 @@ class PlanLayer(nn.Module):
       _require_cuda(t, name)
       if t.get_device() != dev: _same_device(dev, **{name: t})
       if tuple(t.shape) != (B, 1, 4): raise ValueError('%s must be (B,1,4), got %s' % (name, tuple(t.shape)))
-    solver = self._solvers.get(dtype) or self._solver(dtype)
+    solver = self._planar_solver(dtype)
     grids = int(sdfb.shape[0])
     shared = grids == 1 or sdfb.stride(0) == 0
     if env_index is None and not shared and grids != B:
@@ -1333,7 +1350,7 @@ class PlanLayer(nn.Module):
       raise ValueError('path_cells must be a contiguous int32 tensor of shape (%d,%d) (params.path_cap columns), got %s %s' % (B, cap, path_cells.dtype, tuple(path_cells.shape)))
     if tuple(num_cells.shape) != (B,) or num_cells.dtype is not torch.int32 or not num_cells.is_contiguous():
       raise ValueError('num_cells must be a contiguous int32 tensor of shape (%d,), got %s %s' % (B, num_cells.dtype, tuple(num_cells.shape)))
-    solver = self._solvers.get(dtype) or self._solver(dtype)
+    solver = self._planar_solver(dtype)
     grids = int(sdfb.shape[0])
     shared = grids == 1 or sdfb.stride(0) == 0
     if env_index is None and not shared and grids != B:
@@ -1395,6 +1412,43 @@ class PlanLayer(nn.Module):
     _launch(dev, self._pc.prior_samples, solver.h, B, S, st.data_ptr(), go.data_ptr(), _ptr(mn), float(scale), int(seed), int(first_problem), _ptr(nz), th.data_ptr(),
             _ptr(noise_out), info.data_ptr(), _raw_stream(dev))
     return th, noise_out, info
+
+  def heading_lift(self, th2b, params, dtype=None, start_heading=None, goal_heading=None, turns=None, return_turns=False):
+    """Planar trajectories lifted to problems of the x-y-heading robot in ONE launch (dgp_heading_lift; datasets.problem_generation.lift_headings is the documented
+    front end and fills `params`, a _capi.DgpHeadingParams).  A dof 3 layer only.  th2b (B,n,4); start_heading / goal_heading (B,) and turns (B,n): float64 device
+    tensors or None.  -> startb, goalb (B,1,6), thb (B,n,6) of `dtype` (default: th2b's), the (B,n) float64 turns used (None unless return_turns), info (B) int32."""
+    if self.dof != 3: raise ValueError('heading_lift makes problems of the x-y-heading robot: the planner must have dof 3, this one has dof %d' % self.dof)
+    _require_cuda(th2b, 'th2b')
+    B, n, dev = int(th2b.shape[0]), self.num_traj_states, th2b.get_device()
+    if tuple(th2b.shape) != (B, n, 4): raise ValueError('th2b must be (B,%d,4), got %s' % (n, tuple(th2b.shape)))
+    if dtype is None: dtype = th2b.dtype
+    solver = self._solvers.get(dtype) or self._solver(dtype)
+    t2 = th2b.detach().to(dtype).contiguous()
+
+    def doubles(t, name, shape):
+      if t is None: return None
+      _require_cuda(t, name)
+      if t.get_device() != dev: _same_device(dev, **{name: t})
+      if tuple(t.shape) != shape: raise ValueError('%s must be %s, got %s' % (name, shape, tuple(t.shape)))
+      return t.detach().to(torch.float64).contiguous()
+    hs, hg, tin = doubles(start_heading, 'start_heading', (B,)), doubles(goal_heading, 'goal_heading', (B,)), doubles(turns, 'turns', (B, n))
+    device = th2b.device
+    startb = torch.empty((B, 1, 6), dtype=dtype, device=device)
+    goalb = torch.empty((B, 1, 6), dtype=dtype, device=device)
+    thb = torch.empty((B, n, 6), dtype=dtype, device=device)
+    turns_out = torch.empty((B, n), dtype=torch.float64, device=device) if return_turns else None
+    info = torch.empty((B,), dtype=torch.int32, device=device)
+    import ctypes
+    api = _capi.get_api()
+    _launch(dev, api.heading_lift, solver.h, B, ctypes.byref(params), t2.data_ptr(), _ptr(hs), _ptr(hg), _ptr(tin), startb.data_ptr(), goalb.data_ptr(), thb.data_ptr(),
+            _ptr(turns_out), info.data_ptr(), _raw_stream(dev))
+    return startb, goalb, thb, turns_out, info
+
+  def lift_headings(self, th2b, **kw):
+    """datasets.problem_generation.lift_headings(self, th2b, **kw): a planar trajectory (B,n,4) lifted to a problem of the x-y-heading robot
+    -> (startb, goalb (B,1,6), thb (B,n,6), HeadingInfo)."""
+    from ..datasets.problem_generation import lift_headings
+    return lift_headings(self, th2b, **kw)
 
   def sample_prior(self, startb, goalb, num_samples, **kw):
     """datasets.problem_generation.prior_samples(self, startb, goalb, num_samples, **kw): GP-prior trajectory samples for a multi-start -> (thb (B,S,n,d), PriorSampleInfo)."""

@@ -166,3 +166,120 @@ def gp_prior_samples_torch(startb, goalb, noise, total_time_sec, total_time_step
   else:
     m = mean.to(dt_)
   return m[:, None] + scale * xi
+
+
+_HL_PI, _HL_TWO_PI = 3.141592653589793, 6.283185307179586
+_HL_HEADING, _HL_END, _HL_VEL = {'linear': 0, 'tangent': 1}, {'supplied': 0, 'tangent': 1, 'random': 2}, {'keep': 0, 'diff': 1}
+
+
+def _hl_scan(e):
+  """dgp_prior_samples' SCAN along the last axis (include/dgpmp2_hip.h): Hillis-Steele steps inside blocks of 64 indices, then the finished last value of the block
+  before added to every element of a block"""
+  e = e.clone()
+  n = e.shape[-1]
+  for k0 in range(0, n, 64):
+    blk = e[..., k0:k0 + 64]
+    off = 1
+    while off < 64:
+      if off < blk.shape[-1]:
+        new = blk.clone()
+        new[..., off:] = blk[..., :-off] + blk[..., off:]
+        blk.copy_(new)
+      off *= 2
+    if k0 > 0: blk.copy_(e[..., k0 - 1:k0] + blk)
+  return e
+
+
+def _hl_random_ends(seed, problem):
+  """theta_s, theta_g of DGP_END_RANDOM: one Philox4x32-10 block, counter (problem lo, problem hi, 0, 2), key (seed lo, seed hi)"""
+  M = 0xffffffff
+  c0, c1, c2, c3, k0, k1 = problem & M, (problem >> 32) & M, 0, 2, seed & M, (seed >> 32) & M
+  for r in range(10):
+    if r: k0, k1 = (k0 + 0x9E3779B9) & M, (k1 + 0xBB67AE85) & M
+    p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+    c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & M, (p0 >> 32) ^ c3 ^ k1, p0 & M
+  u0, u1 = float(((c0 << 32) | c1) >> 11) * 2.0 ** -53, float(((c2 << 32) | c3) >> 11) * 2.0 ** -53
+  return (-_HL_PI) + u0 * _HL_TWO_PI, (-_HL_PI) + u1 * _HL_TWO_PI
+
+
+def heading_lift_torch(th2b, total_time_sec, start_heading=None, goal_heading=None, heading='tangent', ends='supplied', velocity='diff', blend=None, seed=0,
+                       first_problem=0, turns=None):
+  """Planar trajectories th2b (B,n,4) lifted to problems of the x-y-heading robot -> (startb (B,1,6), goalb (B,1,6), thb (B,n,6), turns (B,n) float64, info (B,)
+  int32): the documented mirror of dgp_heading_lift (include/dgpmp2_hip.h states the rule) as batched torch ops on any device, the CPU included, computed in float64
+  and rounded once to th2b's dtype.  heading 'tangent' | 'linear'; ends 'supplied' | 'tangent' | 'random' or a (start, goal) pair of those; velocity 'diff' | 'keep';
+  blend default max(1, N // 4); start_heading / goal_heading (B,) for supplied ends; turns (B,n): the signed turns to use instead of atan2 of the tangents (what
+  DiffGPMP2Planner.lift_headings(return_turns=True) returned) -- with them the result on the CPU equals the kernel's bit for bit (a device's torch kernels may
+  contract a multiply-add: equal to rounding there), without them to the few ulp between two atan2."""
+  B, n = int(th2b.shape[0]), int(th2b.shape[1])
+  N = n - 1
+  if blend is None: blend = max(1, N // 4)
+  se, ge = (_HL_END[ends], _HL_END[ends]) if isinstance(ends, str) else (_HL_END[ends[0]], _HL_END[ends[1]])
+  hm, vm = _HL_HEADING[heading], _HL_VEL[velocity]
+  if hm == 0 and 1 in (se, ge): raise ValueError("ends='tangent' needs heading='tangent'")
+  if not 1 <= int(blend) <= N: raise ValueError('blend must be in 1..%d, got %r' % (N, blend))
+  dev, f64 = th2b.device, torch.float64
+  T = float(total_time_sec)
+  delta = T / float(N)
+  p = th2b[..., :2].to(f64)
+  x, y = p[..., 0], p[..., 1]
+  idx = torch.arange(n, device=dev)
+  lo, hi = torch.clamp(idx - 1, min=0), torch.clamp(idx + 1, max=N)
+  tx, ty = x[:, hi] - x[:, lo], y[:, hi] - y[:, lo]
+  deg = ((tx == 0) & (ty == 0)) | ~torch.isfinite(tx) | ~torch.isfinite(ty)
+  info = (~(torch.isfinite(x).all(1) & torch.isfinite(y).all(1))).to(torch.int32) * 8
+
+  def end(mode, arr, which):
+    if mode == 0:
+      if arr is None: raise ValueError("ends='supplied' needs start_heading and goal_heading")
+      return torch.as_tensor(arr, dtype=f64, device=dev).reshape(B)
+    if mode == 2: return torch.tensor([_hl_random_ends(int(seed), int(first_problem) + b)[which] for b in range(B)], dtype=f64, device=dev)
+    return torch.zeros(B, dtype=f64, device=dev)
+  ths, thg = end(se, start_heading, 0), end(ge, goal_heading, 1)
+  if se == 0: info = info | (~torch.isfinite(ths)).to(torch.int32) * 8
+  if ge == 0: info = info | (~torch.isfinite(thg)).to(torch.int32) * 8
+  fi = idx.to(f64)
+  if hm == 1:
+    # forward fill: the last valid index at or before each row, the first valid one for leading rows, (1, 0) without any
+    last = torch.cummax(torch.where(deg, torch.full_like(idx, -1).expand(B, n), idx.expand(B, n)), dim=1)[0]
+    any_valid = (~deg).any(1)
+    first = torch.argmax((~deg).to(torch.int32), dim=1)
+    src = torch.where(last >= 0, last, first[:, None].expand(B, n))
+    ux, uy = torch.gather(tx, 1, src), torch.gather(ty, 1, src)
+    ux = torch.where(any_valid[:, None], ux, torch.ones_like(ux))
+    uy = torch.where(any_valid[:, None], uy, torch.zeros_like(uy))
+    if turns is not None: turn = torch.as_tensor(turns, dtype=f64, device=dev).reshape(B, n)
+    else:
+      c = ux[:, :-1] * uy[:, 1:] - uy[:, :-1] * ux[:, 1:]
+      c = torch.where(c == 0, torch.zeros_like(c), c)
+      d = ux[:, :-1] * ux[:, 1:] + uy[:, :-1] * uy[:, 1:]
+      turn = torch.cat((torch.atan2(uy[:, :1], ux[:, :1]), torch.atan2(c, d)), 1)
+    info = info | (~any_valid).to(torch.int32) | deg.any(1).to(torch.int32) * 2 | (turn[:, 1:].abs() > _HL_PI / 2.0).any(1).to(torch.int32) * 4
+    psi = _hl_scan(torch.cat((torch.zeros(B, 1, dtype=f64, device=dev), turn[:, 1:]), 1))
+    wrap = lambda a: a - _HL_TWO_PI * torch.round(a / _HL_TWO_PI)
+    theta_s = turn[:, 0] if se == 1 else ths
+    e_s = torch.zeros_like(ths) if se == 1 else wrap(ths - turn[:, 0])
+    base = theta_s - e_s
+    phi = base[:, None] + psi
+    e_g = torch.zeros_like(thg) if ge == 1 else wrap(thg - phi[:, N])
+    ws = torch.clamp(1.0 - fi / float(blend), min=0.0)
+    wg = torch.clamp(1.0 - (N - idx).to(f64) / float(blend), min=0.0)
+    theta = (phi + ws[None] * e_s[:, None]) + wg[None] * e_g[:, None]
+    theta[:, 0] = theta_s
+    theta[:, N] = phi[:, N] + e_g
+    w0, wN = theta[:, 0], theta[:, N]
+  else:
+    turn = torch.zeros(B, n, dtype=f64, device=dev)
+    theta = ths[:, None] * (N - idx).to(f64)[None] * 1.0 / float(N) * 1.0 + thg[:, None] * fi[None] * 1.0 / float(N) * 1.0
+    w0, wN = ths, thg
+  thb = torch.empty(B, n, 6, dtype=th2b.dtype, device=dev)
+  thb[..., :2] = th2b[..., :2]
+  thb[..., 2] = theta.to(th2b.dtype)
+  if vm == 1:
+    den = (hi - lo).to(f64) * delta
+    thb[..., 3], thb[..., 4] = (tx / den).to(th2b.dtype), (ty / den).to(th2b.dtype)
+    thb[..., 5] = ((theta[:, hi] - theta[:, lo]) / den).to(th2b.dtype)
+  else:
+    thb[..., 3:5] = th2b[..., 2:4]
+    thb[..., 5] = ((wN - w0) / T * 1.0).to(th2b.dtype)[:, None]
+  zeros = torch.zeros(B, 1, 3, dtype=th2b.dtype, device=dev)
+  return torch.cat((thb[:, :1, :3], zeros), -1), torch.cat((thb[:, N:, :3], zeros), -1), thb, turn, info

@@ -763,6 +763,73 @@ int dgp_prior_samples(const DgpHandle* h, int32_t batch, int32_t num_samples,
  * 64-state blocks a wavefront walks (1: one pass; more: the block loop, two passes).  Either pointer may be NULL.  No effect on any result. */
 int dgp_prior_launch_shape(const DgpHandle* h, int32_t* lanes_per_traj, int32_t* blocks);
 
+/* Planar trajectories lifted to problems of the non-holonomic x-y-heading robot (PointRobotXYH, dof 3), ONE launch: th2 (B,n,4) -- a straight line of
+ * dgp_sample_problems, a grid path of dgp_init_paths, its shortcut -- becomes start, goal (B,1,6) and th (B,n,6).  The reference can only build straight_line_trajb
+ * with dof = 3 (utils/planner_utils.py:47-56): a heading linear in time and one constant velocity, which violates the non-holonomic factor
+ * (custom_factors/nonholonomic_factor.py:20, vy cos(theta) - vx sin(theta)) at every state of any path that is not a straight line along both end headings.  Here the
+ * heading follows the path's tangent, continuously (the running sum of the signed turns between consecutive tangents: never wrapped), blended into the end headings,
+ * and the velocities are the path's own central differences; the reference's rule is DGP_HEADING_LINEAR with DGP_VEL_KEEP.
+ * dof == 3 handles only.  Everything below is fp64 whatever io_dtype, FMA contraction off, every operation in the order written, left to right inside a pair of
+ * parentheses; stored values are rounded once.  N = n - 1, Delta = total_time_sec / (double)N, PI = 3.141592653589793, TWO_PI = 6.283185307179586 (doubles),
+ * wrap(a) = a - TWO_PI * rint(a / TWO_PI) (ties to even); (x_i, y_i) columns 0, 1 of row i of th2 converted to double.
+ * Positions.  Columns 0, 1 of th are columns 0, 1 of th2 copied bit for bit (NaN and -0.0 included).
+ * Tangents.  lo = max(i - 1, 0), hi = min(i + 1, N), t_i = (x_hi - x_lo, y_hi - y_lo).  Row i is degenerate where both components are zero or either is not finite.
+ *   u_i is t_i after forward fill: a degenerate row takes the tangent of the nearest earlier non-degenerate row, leading degenerate rows that of the first
+ *   non-degenerate row; with every row degenerate u_i = (1, 0).
+ * Turns (DGP_HEADING_TANGENT).  turn_0 = atan2(u_0.y, u_0.x).  For i >= 1:  c = u_(i-1).x * u_i.y - u_(i-1).y * u_i.x, a zero of either sign counting as +0.0;
+ *   d = u_(i-1).x * u_i.x + u_(i-1).y * u_i.y;  turn_i = atan2(c, d), the fp64 library function (a few ulp from the correctly rounded value).  A path that reverses
+ *   on itself turns by +PI.  turns_in (B,n) doubles, where given, replace ALL n turns (no atan2 is evaluated; the tangents are still formed for the velocities and
+ *   for info).  turns_out (B,n) receives the turns used: feeding it back as turns_in reproduces every output bit for bit.  With DGP_HEADING_LINEAR no turn is formed:
+ *   turns_in is not read and turns_out is all +0.0.
+ *   psi = SCAN(e) with e_0 = 0.0 and e_i = turn_i (i >= 1): psi_0 = 0, psi_i = turn_1 + ... + turn_i in the association order of dgp_prior_samples' SCAN, a function
+ *   of n alone -- inside each block of 64 consecutive indices starting at a multiple of 64, for off = 1, 2, 4, 8, 16, 32 in turn and for all i of the block with
+ *   i % 64 >= off at once, e_i <- e_(i - off) + e_i; then, block after block from the second on, e_i <- c + e_i for every i of the block, c the finished value of the
+ *   last index of the block before.
+ * End headings theta_s, theta_g, each end by its own mode.  DGP_END_SUPPLIED: start_heading[b] / goal_heading[b].  DGP_END_TANGENT (DGP_HEADING_TANGENT only):
+ *   theta_s = turn_0 with e_s = 0, and e_g = 0, by definition.  DGP_END_RANDOM: ONE Philox4x32-10 block per problem, key (seed & 0xffffffff, seed >> 32), counter
+ *   (problem lo, problem hi, 0, 2), problem = first_problem + b (stream 2 next to dgp_sample_problems' 0 and 1); u0, u1 from the four words as for
+ *   dgp_sample_problems (53 bits, [0, 1));  theta_s = (-PI) + u0 * TWO_PI,  theta_g = (-PI) + u1 * TWO_PI.
+ * Headings, DGP_HEADING_TANGENT.  e_s = wrap(theta_s - turn_0);  base = theta_s - e_s;  phi_i = base + psi_i;  e_g = wrap(theta_g - phi_N);
+ *   ws_i = fmax(0, 1 - (double)i / (double)blend),  wg_i = fmax(0, 1 - (double)(N - i) / (double)blend);
+ *   theta_i = (phi_i + ws_i * e_s) + wg_i * e_g, except that row 0 stores theta_s itself and row N stores phi_N + e_g: the representative of the goal heading nearest
+ *   the path's own winding, which is what `goal` carries.
+ * Headings, DGP_HEADING_LINEAR.  theta_i = theta_s * (double)(N - i) * 1.0 / (double)N * 1.0 + theta_g * (double)i * 1.0 / (double)N * 1.0: straight_line_trajb's
+ *   expression and order.  No wrap.
+ * Velocities.  DGP_VEL_KEEP: columns 3, 4 of th are columns 2, 3 of th2 copied bit for bit, and column 5 is (w_N - w_0) / total_time_sec * 1.0 on every row, with
+ *   (w_0, w_N) = (theta_s, theta_g) under DGP_HEADING_LINEAR (the reference's avg_vel is formed from the configurations, not from the rows) and the stored
+ *   (theta_0, theta_N) = (theta_s, phi_N + e_g) under DGP_HEADING_TANGENT.  LINEAR + KEEP on the planar straight line is straight_line_trajb with dof = 3 bit for bit.
+ *   DGP_VEL_DIFF: den = (double)(hi - lo) * Delta;  vx_i = t_i.x / den, vy_i = t_i.y / den (the unfilled tangent);  omega_i = (theta_hi - theta_lo) / den, from the
+ *   headings as doubles, before the store rounding.
+ * start = [x_0, y_0, theta_0, 0, 0, 0] and goal = [x_N, y_N, theta_N, 0, 0, 0], the values row 0 and row N of th store.
+ * info (B): bit 0 every tangent degenerate; bit 1 some row's tangent was degenerate (it was filled); bit 2 some |turn_i| > PI / 2.0, i >= 1 (of the turns used);
+ *   bit 3 a non-finite position or supplied heading.  Bits 0-2 are clear under DGP_HEADING_LINEAR.
+ * th2 (B,n,4), start, goal, th of io_dtype; start_heading, goal_heading (B), turns_in, turns_out (B,n) doubles.  Pointers need only be aligned to their element type
+ * (rows move as 8- / 16-byte vectors where the addresses allow, the same bits either way).  Every output is always written; turns_out and info may be NULL.  A
+ * trajectory's result is a pure function of its own inputs (and of (seed, first_problem + b) for random ends): independent of batch size, position in the batch and
+ * launch shape.
+ * DGP_EINVAL, nothing launched: a NULL handle, params, th2, start, goal or th; dof != 3; batch < 1; an unknown mode; DGP_END_TANGENT under DGP_HEADING_LINEAR;
+ * DGP_END_SUPPLIED with its array NULL; blend outside 1 .. N.  One launch, no atomics, nothing allocated or synchronised: capturable in a HIP graph. */
+#define DGP_HEADING_LINEAR   0   /* theta_i = ths*(N-i)*1.0/N*1.0 + thg*i*1.0/N*1.0, straight_line_trajb's expression and order */
+#define DGP_HEADING_TANGENT  1
+#define DGP_END_SUPPLIED 0       /* start_heading / goal_heading arrays */
+#define DGP_END_TANGENT  1       /* the path's own end tangents (TANGENT heading mode only) */
+#define DGP_END_RANDOM   2       /* Philox */
+#define DGP_VEL_KEEP 0           /* vx, vy copied from th2; one constant omega on every row */
+#define DGP_VEL_DIFF 1           /* finite differences of the stored positions and headings */
+typedef struct DgpHeadingParams {
+  int32_t  heading_mode, start_end, goal_end, velocity_mode;
+  int32_t  blend;          /* rows over which an end's heading error is blended out, 1 .. N */
+  int32_t  reserved;       /* not read */
+  uint64_t seed, first_problem;   /* DGP_END_RANDOM */
+} DgpHeadingParams;        /* 40 bytes */
+int dgp_heading_lift(const DgpHandle* h /* dof 3 */, int32_t batch, const DgpHeadingParams* p,
+                     const void* th2,                                           /* (B,n,4) io_dtype */
+                     const double* start_heading, const double* goal_heading,   /* (B) or NULL */
+                     const double* turns_in,                                    /* (B,n) or NULL */
+                     void* start, void* goal, void* th,                         /* (B,1,6), (B,1,6), (B,n,6) io_dtype */
+                     double* turns_out, int32_t* info,                          /* (B,n), (B); each may be NULL */
+                     void* stream);
+
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
  * hipExtLaunchKernelGGL does -- hipEventElapsedTime(start, stop) is then that kernel's execution time, the quantity
