@@ -3175,6 +3175,11 @@ DGP_HD void gn_lane_program(const GnParams& p, Ctx& cx) {
         }
       }
     }
+    // MODE_SOLVE: info[b] is the OR of the verdicts at the iterates trajectory b itself steps from.  The factorisation below runs for every lane on every
+    // iteration the WAVEFRONT runs: a trajectory that has stopped is factorised again, at its th_out, while a wave neighbour iterates -- a system the
+    // reference never factorises (th_out may well be indefinite under a negative reg), and a verdict that would depend on how long the neighbours run.
+    // So the bits an iteration adds are kept for the lanes whose trajectory entered it `active` only (a ballot: see SpdCheck).
+    [[maybe_unused]] const uint64_t bad_before = ok.bad;
     double e = 0.0, ee = 0.0;
     auto before_pcr = [&](const ErrAcc& a) {
       e = group_sum_to_first<LPT>(cx, a.e); ee = group_sum_to_first<LPT>(cx, a.eext);
@@ -3199,6 +3204,7 @@ DGP_HD void gn_lane_program(const GnParams& p, Ctx& cx) {
       gn_linear_solve<DOF, LPT, C, IO, false, QK, SinvStashBlocks<2 * DOF, C, MODE>::value>(p, cx, b, j, traj_ok, x, mu_s, mu_g, lq, x, dx, acc, ok, before_pcr);
 #endif
     }
+    if constexpr (MODE == MODE_SOLVE) ok.bad = bad_before | (ok.bad & cx.ballot(active));
     DGP_STAMP_NOWAIT(p, cx, 4);
     phase_fence<kPF>();
     if (MODE == MODE_STEP) {

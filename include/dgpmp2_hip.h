@@ -167,7 +167,11 @@ int dgp_gn_step(const DgpHandle* h, int32_t batch,
  * Per trajectory: repeat {dtheta,err,err_ext = step(th); th += dtheta; j++} until
  * ||dtheta||_F < tol_delta or j >= max_iters (utils/planner_utils.py:3-16; the last dtheta IS applied).
  *   th_out (B,n,d); iters (B) int32; err_hist, errext_hist (B,max_iters), entries at or past iters[b] untouched;
- *   err_final (B): error_batch at th_out (diff_gpmp2_planner.py:145,162).  Optional outputs may be NULL. */
+ *   err_final (B): error_batch at th_out (diff_gpmp2_planner.py:145,162).  Optional outputs may be NULL.
+ *   info (B) int32, optional: the OR of dgp_gn_step's flag over the iterates trajectory b ITSELF stepped from, th_k for k < iters[b] (th_0 = th_init):
+ *   1 = one of those systems was not SPD (the reference raises from torch.cholesky in that iteration).  The system at th_out is never part of it, and the
+ *   flag of a trajectory does not depend on which trajectories share its batch or on how many iterations they run.  Once a trajectory is flagged its
+ *   dtheta is not meaningful: it keeps iterating to max_iters (or until a step norm below tol_delta turns up) and its th_out is to be discarded. */
 int dgp_gn_solve(const DgpHandle* h, int32_t batch,
                  const void* th_init, const void* start, const void* goal,
                  const DgpSdf* sdf, const DgpCovs* covs,
@@ -231,7 +235,9 @@ int dgp_eval_errors_backward(const DgpHandle* h, int32_t batch,
 
 /* dgp_gn_solve with the trajectory history the backward pass needs: th_hist (max_iters, B, n, d) in fp64 WHATEVER the handle's io_dtype
  * (dtheta_k = th_{k+1} - th_k is formed from it), row (k, b) = th_k of trajectory b for k < iters[b]; rows at or past iters[b] are not
- * written.  iters must be given with th_hist.  th_hist == NULL: exactly dgp_gn_solve.  num_states <= 256. */
+ * written.  iters must be given with th_hist.  th_hist == NULL: exactly dgp_gn_solve.  num_states <= 256.
+ * info (B): as dgp_gn_solve's -- the OR of the step's SPD flag over the rows (k, b), k < iters[b], of th_hist, i.e. over the iterates trajectory b itself
+ * stepped from; th_out and the other trajectories of the batch have no part in it. */
 int dgp_gn_solve_traced(const DgpHandle* h, int32_t batch,
                         const void* th_init, const void* start, const void* goal,
                         const DgpSdf* sdf, const DgpCovs* covs,

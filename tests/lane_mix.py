@@ -141,8 +141,9 @@ def r11(a):
 def is_scalar(cov): return cov.startswith('scalar')
 
 
-def make(dof, lpt, c, n, cov, vel=False, waves=None, seed=0, nan=True, io='f32', grid=None):
+def make(dof, lpt, c, n, cov, vel=False, waves=None, seed=0, nan=True, io='f32', grid=None, reg=0.1):
   """-> Batch with p, th, start, goal, sdf, qc, ow, eps, q_full (harness.Backend's arguments), and B, lpt, c, waves, nan_rows, kinds.
+  reg: the diagonal shift of Lambda = A^T K A + reg I (no other number of the batch depends on it; tests/spd_cases.py lowers it below zero).
   'scalar' modes: qc (B, n-1) the scalars, qc_dense (B, n-1, dof, dof) the blocks s_k Q_c_inv the oracles take, raw_out ('scalar_raw': the learn
   module's output vector [q_k, o_i, e_i] whose squares are qc, ow, eps) .  grid (H, W): one grid per trajectory, the shared one cropped to H x W
   (res = 10 / W) plus a constant offset per trajectory."""
@@ -156,7 +157,7 @@ def make(dof, lpt, c, n, cov, vel=False, waves=None, seed=0, nan=True, io='f32',
     A = rs.randn(dof, dof) * 0.3
     kw['Q_c_inv'] = np.eye(dof) + A @ A.T
   if cov in ('static_diag', 'scalar_diag'): kw['Q_c_inv'] = QC_DIAG(dof)
-  p = O.OracleParams(dof=dof, total_time_step=n - 1, reg=0.1, epsilon_dist=0.3, use_vel_limits=vel, **kw)
+  p = O.OracleParams(dof=dof, total_time_step=n - 1, reg=reg, epsilon_dist=0.3, use_vel_limits=vel, **kw)
   sdf = O.circles_sdf(G, CIRCLES)[None, None] if grid is None else O.circles_sdf(max(grid), CIRCLES)[None, None, :grid[0], :grid[1]]
   slot = np.arange(B) % T
   wave = np.arange(B) // T

@@ -203,3 +203,63 @@ def test_emul_call_forms(i):
   compared = CF.run_config(b, c, groups, fails)
   assert b.guard_checks > 0 and b.input_checks > 0 and compared > 0
   assert not fails, '%d call forms differ from the canonical call:\n' % len(fails) + '\n'.join(map(str, fails[:40]))
+
+
+# ---- the per-trajectory SPD flag `info` against an inertia reference (tests/spd_cases.py): the CPU-only conditions on the inputs and the two references, then a
+# trimmed selection of tests/test_hip_spd_flag.py through the emulator (every lane a thread: n <= 64)
+import lane_mix as LM
+import spd_cases as SC
+
+_NT = max(1, min(16, os.cpu_count() or 1))
+
+
+@pytest.mark.parametrize('dof', [2, 3])
+def test_spd_references_and_conditions(dof):
+  """Oracle alone, every configuration tests/test_hip_spd_flag.py runs: at most 10 % of the trajectories of a (configuration, rung) undecided or excluded by the
+  loop's chain; a rung with a decided-clean and a decided-flagged trajectory in one wavefront (shapes with two or more trajectories per wavefront); and for
+  n d <= 256 the dense numpy oracle -- eigvalsh(LAM).min() <= 0 -- agrees with the long-double C oracle on every decided trajectory at every rung, and
+  spd_cases.diag_lam (the scale of delta at any n) is the dense LAM's diagonal."""
+  bad = []
+  compared = 0
+  for cfg, grid, seed in SC.all_configs(dof):
+    bt = SC.batch(dof, cfg, grid, seed)
+    refs = SC.references(bt, _NT)
+    bad += SC.check_conditions(bt, refs)
+    if bt.n * 2 * dof > 256: continue
+    for reg, (r, _, _) in refs.items():
+      lam = SC.dense_lam(bt, bt.th, reg)
+      dg = np.einsum('bii->bi', lam)
+      if not np.allclose(SC.diag_lam(bt, bt.th, reg), dg, rtol=1e-12, atol=1e-12 * np.abs(dg).max()): bad.append('%s reg %g: diag_lam differs from the dense diagonal' % (bt.tag, reg))
+      dense = (np.linalg.eigvalsh(lam).min(1) <= 0).astype(np.int32)
+      bad += SC._flag_fails(bt, 'reg %g dense oracle' % reg, dense, r.verdict, r.decided)
+      compared += int(r.decided.sum())
+  assert compared > 1000
+  assert not bad, '\n'.join(bad)
+
+
+# one shape per LPT ((16,4), (32,2), (64,1)) and each covariance family at d = 4 -- the families spread over the three shapes --, and one d = 6 Woodbury
+# configuration; every one runs the fused loop (and the traced loop where static) on spd_cases.trimmed_rungs
+_SPD_SHAPES = ((16, 4), (32, 2), (64, 1))
+_SPD_EMUL = [(2, (16, 4, 64, 'static', False)), (2, (16, 4, 61, 'qfull', False)), (2, (32, 2, 61, 'static_full', False)), (2, (32, 2, 64, 'perstate', False)),
+             (2, (32, 2, 61, 'scalar', False)), (2, (64, 1, 64, 'static_diag', True)), (2, (64, 1, 64, 'perstate', True)), (3, (16, 4, 64, 'static', False))]
+
+
+def test_spd_emulator_selection():
+  covs = set(cf[3].split('_raw')[0] for d, cf in _SPD_EMUL if d == 2)
+  assert covs >= {'static', 'static_full', 'static_diag', 'perstate', 'qfull', 'scalar'} and set(cf[:2] for _, cf in _SPD_EMUL) == set(_SPD_SHAPES), _SPD_EMUL
+  assert all(cf in LM.configs(d) for d, cf in _SPD_EMUL)      # (the GPU test's own configurations, seeded alike)
+  assert all(cf[2] <= 64 for _, cf in _SPD_EMUL) and any(d == 3 and LM.expected_variant(*cf) in (3, 4) for d, cf in _SPD_EMUL)
+
+
+@pytest.mark.parametrize('dof,cfg', _SPD_EMUL, ids=lambda v: v if isinstance(v, int) else '%d_%d_n%d_%s' % v[:4])
+def test_emul_spd_flag(dof, cfg, monkeypatch):
+  """tests/test_hip_spd_flag.py on the emulator: lever A on three rungs (f64; one configuration of each shape on the mixed rung in f32 as well), lever B where the mode has
+  per-call covariance tensors"""
+  monkeypatch.setenv('DGP_FORCE_SHAPE', '%d,%d' % cfg[:2])
+  bt = SC.batch(dof, cfg, None, 1000 * dof + 10 * cfg[0] + cfg[1])
+  be = harness.Backend('emul')
+  only = SC.trimmed_rungs(bt, SC.references(bt, _NT))
+  bad = SC.run_ladder(be, bt, 'f64', nthreads=_NT, only=only)
+  if cfg[3] in ('qfull', 'static_full', 'static_diag'): bad += SC.run_ladder(be, bt, 'f32', nthreads=_NT, alone=False, rotation=False, only=only[1:2])
+  if cfg[3] in SC.LEVER_B_COVS: bad += SC.run_lever_b(be, bt, 'f64', nthreads=_NT)
+  assert not bad, '%d failures:\n' % len(bad) + '\n'.join(bad[:40])

@@ -1228,3 +1228,43 @@ def test_step_and_autograd_match_the_reference_at_other_constants(golden):
   planner.step(T(g['th']), T(g['start']), T(g['goal']), im, sdf)
   usg, ugp, uob = planner.unweighted_errors_batch(T(g['th']), sdf)
   for got, k in ((usg, 'unw_sg'), (ugp, 'unw_gp'), (uob, 'unw_obs')): assert rel_err(got.cpu().numpy(), g[k]) < 1e-11, k
+
+
+def test_plan_layer_spd_flags_on_a_mixed_batch():
+  """The SPD flags through PlanLayer on a batch that mixes healthy and indefinite trajectories inside its wavefronts (tests/spd_cases.py, lever B: one GP block
+  of four of the seven trajectories times -50, per-state covariances): check_spd=True raises from forward() and from forward_with_errors(), `last_info` holds
+  the C-ABI's flags per trajectory -- which are the long-double oracle's verdicts --, and without check_spd nothing raises and `last_info` is the same tensor of flags."""
+  import harness
+  import lane_mix as LM
+  import spd_cases as SC
+  from dgpmp2_amd.robot_models import PointRobot2D
+  from dgpmp2_amd.gpmp2.plan_layer import PlanLayer
+  cfg = (32, 2, 64, 'perstate', False)
+  assert cfg in LM.configs(2)
+  bt = SC.batch(2, cfg, None, 2322)
+  bb = SC.negate_blocks(bt, SC.lever_b_picks(bt)[0])
+  r = SC.reference(bb, bb.p.reg)
+  assert r.decided.all() and 0 < r.verdict.sum() < bb.B and len(SC.mixed_waves(bb, r))
+  p, B, n = bb.p, bb.B, bb.n
+  t = lambda v: torch.tensor(v, dtype=torch.float64)
+  gp = {'Q_c_inv': torch.eye(2, dtype=torch.float64), 'K_s': t(p.K_s), 'K_g': t(p.K_g), 'K_v': t(p.K_v), 'v_x': [p.v_x], 'v_y': [p.v_y]}
+  ob = {'cost_sigma': t(p.cost_sigma), 'epsilon_dist': t(p.epsilon_dist)}
+  pp = {'dof': 2, 'state_dim': 4, 'total_time_sec': p.total_time_sec, 'total_time_step': n - 1}
+  op = {'method': 'gauss_newton', 'reg': p.reg, 'plan_time': float('inf'), 'max_iters': 3, 'tol_err': 1e-3, 'tol_delta': 1e-4}
+  ev = {'x_lims': list(p.x_lims), 'y_lims': list(p.y_lims)}
+  robot = PointRobot2D(torch.tensor(p.radius, dtype=torch.float64), B, n, use_cuda=True)
+  args = (T(bb.th), T(bb.start), T(bb.goal), None, T(bb.sdf).expand(B, 1, *bb.sdf.shape[-2:]), T(bb.qc), T(bb.ow).reshape(B, n, 1, 1), T(bb.eps).reshape(B, n, 1, 1))
+  capi = harness.Backend('hip').step(p, bb.th, bb.start, bb.goal, bb.sdf, **LM.kkw(bb, 'f64'))[3]
+  assert np.array_equal(capi, r.verdict), (capi, r.verdict)
+  flags = torch.from_numpy(capi).to(DEV)
+  for check in (True, False):
+    layer = PlanLayer(gp, ob, pp, op, ev, robot, batch_size=B, use_cuda=True, check_spd=check)
+    for call in (layer, layer.forward_with_errors):
+      layer.last_info = None
+      if check:
+        with pytest.raises(RuntimeError, match='not positive definite'):
+          call(*args)
+      else:
+        out = call(*args)
+        assert torch.isfinite(out[0][flags == 0]).all()
+      assert layer.last_info.dtype == torch.int32 and torch.equal(layer.last_info, flags), (check, layer.last_info, flags)
