@@ -34,6 +34,12 @@ DGP_MAX_NUM_INTER = 1023
 DGP_HEADING_LINEAR, DGP_HEADING_TANGENT = 0, 1      # dgp_heading_lift: DgpHeadingParams.heading_mode
 DGP_END_SUPPLIED, DGP_END_TANGENT, DGP_END_RANDOM = 0, 1, 2      # ... start_end / goal_end
 DGP_VEL_KEEP, DGP_VEL_DIFF = 0, 1      # ... velocity_mode
+# dgp_select_samples: status bits of a sample, columns of its (B, DGP_SELECT_COUNT) float64 problem summary in the header's order (DGP_SELECT_*)
+DGP_SEL_COLLIDING, DGP_SEL_OUTSIDE, DGP_SEL_NON_FINITE, DGP_SEL_EXCLUDED = 1, 2, 4, 8
+SELECT_NAMES = ('solved', 'num_accepted', 'best_index', 'best_score', 'best_max_penetration', 'best_status')
+DGP_SELECT_SOLVED, DGP_SELECT_NUM_ACCEPTED, DGP_SELECT_BEST_INDEX, DGP_SELECT_BEST_SCORE, DGP_SELECT_BEST_MAX_PENETRATION, DGP_SELECT_BEST_STATUS = range(6)
+DGP_SELECT_COUNT = len(SELECT_NAMES)
+DGP_MAX_SELECT_SAMPLES = 1024      # the keys of a problem's samples stay in LDS
 DGP_MAX_PRIOR_SAMPLES = 1 << 24      # dgp_prior_samples: the sample index shares a Philox counter word with the stream tag
 # entries of dgp_step_loss' (DGP_LOSS_COUNT) float64 terms (one_step_loss's return order) and columns of its (B, DGP_LOSS_PER_TRAJ) float64 per_traj
 LOSS_NAMES = ('total', 'pos', 'vel', 'cov', 'gp', 'sg', 'obs', 'ext')
@@ -93,6 +99,10 @@ class DgpHeadingParams(C.Structure):
               ('seed', C.c_uint64), ('first_problem', C.c_uint64)]
 
 
+class DgpSelectParams(C.Structure):
+  _fields_ = [('struct_size', C.c_uint32), ('num_inter', C.c_int32), ('eps', C.c_double), ('sample_major', C.c_int32), ('require_inside', C.c_int32)]
+
+
 class DgpLossWeights(C.Structure):
   _fields_ = [('vel_loss_lambda', C.c_double), ('ext_obs_lambda', C.c_double), ('ext_loss_weight', C.c_double)]
 
@@ -108,7 +118,7 @@ class CApi(object):
 
   SYMBOLS = ('abi_version', 'last_error', 'create', 'destroy', 'num_factor_rows', 'launch_shape', 'step_kernel_variant', 'gn_step', 'gn_solve',
              'eval_errors', 'gn_step_backward', 'eval_errors_backward', 'gn_solve_traced', 'gn_solve_backward', 'gn_step_errors',
-             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'shortcut_paths', 'prior_samples', 'prior_launch_shape', 'heading_lift', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
+             'gn_step_errors_backward', 'sum_partial_grids', 'square_covariances', 'square_covariances_backward', 'sdf_2d_workspace_bytes', 'sdf_2d', 'traj_metrics', 'sample_problems', 'obstacle_maps', 'init_paths', 'shortcut_paths', 'prior_samples', 'prior_launch_shape', 'heading_lift', 'select_samples', 'select_launch_shape', 'gp_interpolate', 'step_loss', 'step_loss_backward', 'sdf_lookup', 'sdf_lookup_backward', 'time_next_launch', 'event_create', 'event_destroy', 'event_elapsed_ms')
 
   def __init__(self, path, prefix='dgp_'):
     if not os.path.exists(path):
@@ -194,6 +204,14 @@ class CApi(object):
     if self.heading_lift is not None:
       self.heading_lift.restype = C.c_int
       self.heading_lift.argtypes = [vp, i32, C.POINTER(DgpHeadingParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    # dgp_select_samples: no twin in the emulator either
+    self.select_samples = getattr(self.lib, prefix + 'select_samples', None)
+    self.select_launch_shape = None
+    if self.select_samples is not None:
+      self.select_samples.restype = C.c_int
+      self.select_samples.argtypes = [vp, i32, i32, vp, vp, vp, C.POINTER(DgpSdf), vp, C.POINTER(DgpSelectParams), vp, vp, vp, vp, vp, vp, vp]
+      self.select_launch_shape = f('select_launch_shape'); self.select_launch_shape.restype = C.c_int
+      self.select_launch_shape.argtypes = [vp, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     # dgp_gp_interpolate: no twin in the emulator either
     self.gp_interpolate = getattr(self.lib, prefix + 'gp_interpolate', None)
     if self.gp_interpolate is not None:
@@ -630,6 +648,31 @@ class Solver(object):
       raise NotImplementedError('%s does not export %sheading_lift (the CPU emulator has no twin of the lift kernel)' % (self.api.path, self.api.prefix))
     self.api.check(self.api.heading_lift(self.handle, int(batch), C.byref(params) if params is not None else None, th2, start_heading, goal_heading, turns_in, start, goal, th,
                                          turns_out, info, stream))
+
+  @staticmethod
+  def select_params(num_inter=7, eps=0.0, sample_major=False, require_inside=True):
+    """DgpSelectParams: K and epsilon of the dense check (as dgp_gp_interpolate), the layout of th / score / exclude ((B,S,..) or sample-major (S,B,..)) and whether a
+    sample that leaves the handle's limits is rejected."""
+    return DgpSelectParams(C.sizeof(DgpSelectParams), int(num_inter), float(eps), 1 if sample_major else 0, 1 if require_inside else 0)
+
+  def select_samples(self, batch, num_samples, th, params, score=None, exclude=None, sdf=None, env_index=None, th_best=None, best=None, order=None, status=None,
+                     sample_summary=None, problem_summary=None, stream=None):
+    """dgp_select_samples: per problem the dense check, the total order and the gather of its num_samples optimised trajectories th (B,S,n,d) -- (S,B,n,d) with
+    params.sample_major -- of the I/O type; score (I/O type) and exclude (int32) laid out like th's leading axes, or None; sdf with the stride between PROBLEMS'
+    grids, or None; outputs th_best (B,n,d), best (B), order / status (B,S) int32, sample_summary (B,S,DGP_DENSE_COUNT) and problem_summary (B,DGP_SELECT_COUNT)
+    float64, each or None; one launch."""
+    if self.api.select_samples is None:
+      raise NotImplementedError('%s does not export %sselect_samples (the CPU emulator has no twin of the selection kernel)' % (self.api.path, self.api.prefix))
+    self.api.check(self.api.select_samples(self.handle, int(batch), int(num_samples), th, score, exclude, C.byref(sdf) if sdf is not None else None, env_index,
+                                           C.byref(params) if params is not None else None, th_best, best, order, status, sample_summary, problem_summary, stream))
+
+  def select_launch_shape(self, num_samples, num_inter):
+    """(lanes per trajectory, wavefronts of a problem's workgroup, passes over the samples) dgp_select_samples launches: what its own dispatch reads."""
+    if self.api.select_samples is None:
+      raise NotImplementedError('%s does not export %sselect_launch_shape (the CPU emulator has no twin of the selection kernel)' % (self.api.path, self.api.prefix))
+    l, w, p = C.c_int32(), C.c_int32(), C.c_int32()
+    self.api.check(self.api.select_launch_shape(self.handle, int(num_samples), int(num_inter), C.byref(l), C.byref(w), C.byref(p)))
+    return l.value, w.value, p.value
 
   def eval_errors_backward(self, batch, th, start, goal, sdf, covs, g_err_ext=None, g_unw_sg=None, g_unw_gp=None, g_unw_obs=None,
                            g_th=None, g_start=None, g_goal=None, g_sdf=None, g_sdf_batch_stride=0, g_eps=None, stream=None, g_sdf_copies=1):

@@ -16,7 +16,8 @@
 // Reduction: every lane keeps an fp64 partial sum, a maximum with its index, a count and a minimum first index of its dense states, then a butterfly over the
 // trajectory's LPT lanes -- a fixed order that depends on N_d and LPT only: no atomics, no LDS, bit-identical results from run to run, for either grid layout and
 // wherever the trajectory sits in the batch.  Lanes 0 .. 5 of a trajectory store its DGP_DENSE_COUNT doubles as one contiguous run.  Lane groups past the end of a
-// ragged batch recompute the last trajectory and store nothing (no divergent shuffles).
+// ragged batch recompute the last trajectory and store nothing (no divergent shuffles).  The walk and the reductions live in dgp_dense_walk.h, shared with
+// select_samples.hip (dgp_select_samples), whose per-sample summary is this kernel's bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #ifndef DGP_TL
@@ -24,6 +25,7 @@
 #endif
 #include "dgp_host.h"
 #include "dgp_launch.h"
+#include "dgp_dense_walk.h"
 
 #pragma clang fp contract(off)
 
@@ -42,45 +44,6 @@ struct InterpArgs {
 };
 static_assert(sizeof(InterpArgs) <= 4096, "kernel-argument segment");
 
-constexpr int NO_INDEX = 0x7fffffff;
-
-template <int LPT>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-template <int LPT>
-__device__ __forceinline__ int group_sum_i(int v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-template <int LPT>
-__device__ __forceinline__ int group_min_i(int v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) {
-    const int o = __shfl_xor(v, m);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-// the maximum with its index: a NaN wins over every number (torch.max), the smaller index wins between equals (and between NaNs).
-// Symmetric: both partners of an exchange end with the same pair.
-template <int LPT>
-__device__ __forceinline__ void group_argmax(double& v, int& idx) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) {
-    const double ov = __shfl_xor(v, m);
-    const int oi = __shfl_xor(idx, m);
-    const bool vn = v != v, on = ov != ov;
-    const bool greater = (on && !vn) || ov > v, equal = (on && vn) || ov == v;
-    const bool take = greater || (equal && oi < idx);
-    v = take ? ov : v;
-    idx = take ? oi : idx;
-  }
-}
-
 template <int DOF, typename IO, int LPT>
 __global__ void __launch_bounds__(64) gp_interpolate_kernel(const InterpArgs a) {
   constexpr int D = 2 * DOF, TPW = 64 / LPT;
@@ -95,68 +58,13 @@ __global__ void __launch_bounds__(64) gp_interpolate_kernel(const InterpArgs a) 
   IO* dense = (IO*)a.th_dense + b * nd * D;
   IO* ocost = (IO*)a.dense_cost + b * nd;
   const bool look = a.dense_cost != nullptr || a.summary != nullptr;      // wave-uniform
-  const double dt = p.dt, fk1 = (double)k1;
-  double s_pen = 0.0, m_pen = -__builtin_huge_val();
-  int m_idx = NO_INDEX, cnt = 0, first = NO_INDEX;
-  for (int m = l; m < nd; m += LPT) {
-    const int i = m / k1, j = m - i * k1;
-    const int i1 = i + 1 < n ? i + 1 : n - 1;      // clamped: the last dense state is a copy (j == 0), the row is unused
-    IO r0[D], r1[D];
-#pragma unroll
-    for (int c = 0; c < D; ++c) { r0[c] = th[(int64_t)i * D + c]; r1[c] = th[(int64_t)i1 * D + c]; }
-    // the eight coefficients, in the header's operation order
-    const double s = (double)j / fk1;
-    const double s2 = s * s;
-    const double s3 = s2 * s;
-    const double a0 = (1.0 - 3.0 * s2) + 2.0 * s3;
-    const double a1 = dt * ((s - 2.0 * s2) + s3);
-    const double a2 = 3.0 * s2 - 2.0 * s3;
-    const double a3 = dt * (s3 - s2);
-    const double b2 = (6.0 * (s - s2)) / dt;
-    const double b0 = -b2;
-    const double b1 = (1.0 - 4.0 * s) + 3.0 * s2;
-    const double b3 = 3.0 * s2 - 2.0 * s;
-    const bool copy = j == 0;
-    double q[D];
-#pragma unroll
-    for (int c = 0; c < DOF; ++c) {
-      const double x0 = (double)r0[c], v0 = (double)r0[DOF + c], x1 = (double)r1[c], v1 = (double)r1[DOF + c];
-      q[c] = ((a0 * x0 + a1 * v0) + a2 * x1) + a3 * v1;
-      q[DOF + c] = ((b0 * x0 + b1 * v0) + b2 * x1) + b3 * v1;
-    }
-    if (a.th_dense != nullptr && on) {
-#pragma unroll
-      for (int c = 0; c < D; ++c) dense[(int64_t)m * D + c] = copy ? r0[c] : (IO)q[c];      // a support state passes through untouched, bit for bit
-    }
-    if (look) {
-      double cost, hx, hy;
-      dgp::obstacle_eval<IO>(p, grid, copy ? (double)r0[0] : q[0], copy ? (double)r0[1] : q[1], a.eps, cost, hx, hy);
-      if (a.dense_cost != nullptr && on) ocost[m] = (IO)cost;
-      const bool interior = m >= 1 && m < nd - 1;      // collision_metrics' convention: the first and the last state are left out
-      s_pen += interior ? cost : 0.0;
-      const bool hit = interior && cost != 0.0;        // torch.nonzero: a NaN counts
-      cnt += hit ? 1 : 0;
-      first = (hit && m < first) ? m : first;
-      const bool take = interior && ((cost != cost && !(m_pen != m_pen)) || cost > m_pen);      // m rises: the smallest index of equals stays
-      m_pen = take ? cost : m_pen;
-      m_idx = take ? m : m_idx;
-    }
-  }
+  dgp_dense::Partials r;
+  dgp_dense::Flags unused = {false, false};
+  dgp_dense::walk<DOF, IO, LPT, false>(p, th, grid, (a.th_dense != nullptr && on) ? dense : nullptr, (a.dense_cost != nullptr && on) ? ocost : nullptr, look, a.eps, k1, nd, l,
+                                       r, dgp_dense::Limits{0.0, 0.0, 0.0, 0.0}, unused);      // (dgp_dense_walk.h: shared with dgp_select_samples, the same bits)
   if (a.summary == nullptr) return;
-  s_pen = group_sum<LPT>(s_pen);
-  group_argmax<LPT>(m_pen, m_idx);
-  cnt = group_sum_i<LPT>(cnt);
-  first = group_min_i<LPT>(first);
-  double out;
-  switch (l) {
-    case DGP_DENSE_IN_COLL: out = cnt > 0 ? 1.0 : 0.0; break;
-    case DGP_DENSE_NUM_COLLIDING: out = (double)cnt; break;
-    case DGP_DENSE_AVG_PENETRATION: out = s_pen / (double)(nd - 2); break;
-    case DGP_DENSE_MAX_PENETRATION: out = m_pen; break;
-    case DGP_DENSE_FIRST_COLLIDING: out = first == NO_INDEX ? -1.0 : (double)first; break;
-    case DGP_DENSE_WORST_INDEX: out = (double)m_idx; break;
-    default: out = 0.0; break;
-  }
+  dgp_dense::reduce<LPT>(r);
+  const double out = dgp_dense::summary_column(l, r, nd);
   if (on && l < DGP_DENSE_COUNT) a.summary[b * DGP_DENSE_COUNT + l] = out;
 }
 

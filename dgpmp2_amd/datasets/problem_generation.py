@@ -380,7 +380,7 @@ def sample_problems(planner_or_layer, sdfb, num_problems=None, env_index=None, c
 
 
 def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, first_diagonal=True, require_collision_free=True, dataset_type=None, num_envs=None,
-                     im_size=None, obstacle_params=None, init='straight', check_inter=0, heading=None, ends=None, velocity=None, blend=None, **params):
+                     im_size=None, obstacle_params=None, init='straight', check_inter=0, heading=None, ends=None, velocity=None, blend=None, multistart=0, multistart_scale=1.0, **params):
   """The reference's generation chain for a batch of environments, on the device until the files are written:
     0. images=None: generate_obstacle_maps(planner, dataset_type, num_envs, im_size, seed=seed, **obstacle_params) makes the images (uint8); an environment whose
        map is flagged capped or overlapping is dropped before anything else runs           (generate_2d_dataset.py:194-208; the reference never returns such a map)
@@ -394,6 +394,9 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
        check_inter > 0: the verdict is that of the GP-interpolated dense trajectory with check_inter states inside every interval, planner.interpolate(th_opt,
        check_inter, sdfb, eps=0).in_collision -- a trajectory whose support states straddle an obstacle is caught (the reference's 'total_check_step' /
        'use_gp_inter' keys, gpmp2_planner.py:29-41, name this check and nothing implements it); 0, the default: the support states only, as the reference
+       multistart = S > 0: steps 3 and 4 are planner.plan_multistart around the initial trajectories -- S samples of the GP prior with mean th_init and spread
+       multistart_scale plus th_init itself, the fused loop over all of them, the selection with check_inter states per interval -- th_opt is the chosen
+       trajectory and the verdict is `not solved` (no candidate ended free and inside the limits); 0, the default: one start per problem, every output unchanged
     5. write_environment / write_problem / write_meta
   images: (E,H,W) or (E,1,H,W) device tensor, free space > 0.75.  An environment with a problem whose sampling hit max_draws is dropped; so is one with a planned
   trajectory in collision when require_collision_free is set (the reference drops an environment by exception, :247-265).  Written environments are numbered densely.
@@ -418,7 +421,7 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
     if good:
       r = generate_dataset(root_dir, mode, gen[sel], planner, probs_per_env, seed=seed, first_diagonal=first_diagonal,
                            require_collision_free=require_collision_free, init=init, check_inter=check_inter, heading=heading, ends=ends, velocity=velocity,
-                           blend=blend, **params)
+                           blend=blend, multistart=multistart, multistart_scale=multistart_scale, **params)
     else:
       write_meta(root_dir, mode, 0, int(probs_per_env), {'x_lims': [float(v) for v in planner.env_params['x_lims']], 'y_lims': [float(v) for v in planner.env_params['y_lims']]},
                  int(gen.shape[-1]))
@@ -453,9 +456,15 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
     if path_info.heading is not None: startb, goalb = path_info.heading.start, path_info.heading.goal      # rows 0 and N of th_initb: the goal heading nearest THIS path's winding
   sdfb = sdf.index_select(0, env_index.long())      # one grid per problem, what forward() takes
   imb = (im > 0.75).to(sdf.dtype).unsqueeze(1).index_select(0, env_index.long())
+  multi = None
   with torch.no_grad():
-    th_opt = planner.forward(th_initb, startb, goalb, imb, sdfb)[0]
-    if int(check_inter) > 0: in_coll = planner.interpolate(th_opt, int(check_inter), sdfb, eps=0.0).in_collision
+    if int(multistart) > 0:
+      th_opt, multi = planner.plan_multistart(startb, goalb, sdfb, int(multistart), th_extra=th_initb[:, None], seed=seed, mean=th_initb, scale=multistart_scale,
+                                              num_inter=int(check_inter), eps=0.0)
+      in_coll = ~multi.select.solved
+    else: th_opt = planner.forward(th_initb, startb, goalb, imb, sdfb)[0]
+    if multi is not None: pass
+    elif int(check_inter) > 0: in_coll = planner.interpolate(th_opt, int(check_inter), sdfb, eps=0.0).in_collision
     else: in_coll = planner.trajectory_metrics(th_opt, sdfb, eps=0.0).in_collision
   capped_h, coll_h = info.capped.view(E, P).any(1).cpu().numpy(), in_coll.view(E, P).any(1).cpu().numpy()
   s_h, g_h, th_h = startb.cpu().numpy(), goalb.cpu().numpy(), th_opt.cpu().numpy()
@@ -473,4 +482,4 @@ def generate_dataset(root_dir, mode, images, planner, probs_per_env, seed=0, fir
       kept.append(e)
   write_meta(root_dir, mode, len(kept), P, {'x_lims': x_lims, 'y_lims': y_lims}, W)
   return {'num_envs': len(kept), 'kept': kept, 'dropped': dropped, 'start': startb, 'goal': goalb, 'th_init': th_initb, 'th_opt': th_opt, 'info': info,
-          'in_coll': in_coll, 'path_info': path_info}
+          'in_coll': in_coll, 'path_info': path_info, **({'multistart': multi} if multi is not None else {})}

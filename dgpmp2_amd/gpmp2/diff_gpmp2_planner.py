@@ -139,6 +139,16 @@ class _SquaredCovs(torch.autograd.Function):
     return (2.0 * out[:, 0, :] * g_sq).unsqueeze(1), None, None, None, None
 
 
+class MultiStartInfo(object):
+  """What DiffGPMP2Planner.plan_multistart reports, device tensors: `select` the SelectInfo of the selection (best, solved, status, order, ...), `prior` the
+  PriorSampleInfo of the drawn samples (B,S), and per candidate (B, S + E), the drawn samples first: `iters` the Gauss-Newton iterations run, `err_final` the final
+  error (the selection's score), `spd_info` the solve's flags (non-zero: a system was not positive definite; the selection's exclude)."""
+  __slots__ = ('select', 'prior', 'iters', 'err_final', 'spd_info')
+
+  def __init__(self, select, prior, iters, err_final, spd_info):
+    self.select, self.prior, self.iters, self.err_final, self.spd_info = select, prior, iters, err_final, spd_info
+
+
 class DiffGPMP2Planner(nn.Module):
   def __init__(self, gp_params, obs_params, planner_params, optim_params, env_params, robot_model, learn_params=None, batch_size=1,
                use_cuda=False, learn_module_conv=None, learn_module_fcn=None):
@@ -497,6 +507,55 @@ class DiffGPMP2Planner(nn.Module):
     capability the reference's 'total_check_step' / 'use_gp_inter' keys name (gpmp2_planner.py:29-41).  No autograd; usable inside graphed_iteration /
     torch.cuda.graph."""
     return self.plan_layer.interpolate(thb, num_inter, sdfb, eps, return_cost)
+
+  def select_samples(self, thb, sdfb=None, **kw):
+    """plan_layer.select_samples(thb, sdfb, **kw): multi-start selection in one launch -- per problem the dense check of its S optimised trajectories, their
+    total order and the chosen one -> (th_best (B,n,d), SelectInfo)."""
+    return self.plan_layer.select_samples(thb, sdfb, **kw)
+
+  def plan_multistart(self, startb, goalb, sdfb, num_samples, th_extra=None, seed=0, first_problem=0, mean=None, scale=1.0, num_inter=7, eps=0.0, require_inside=True,
+                      max_iters=None, tol_delta=None):
+    """A multi-start per problem with nothing leaving the device: num_samples GP-prior samples around `mean` (None: the prior mean; dgp_prior_samples), the
+    deterministic candidates th_extra (B,E,n,d) behind them (the straight line, the grid path), the fused Gauss-Newton loop over all of them (dgp_gn_solve), and
+    the selection (dgp_select_samples: dense check with num_inter states per interval at epsilon eps, score = the final error, exclude = the solve's SPD flags).
+    A shared grid ((1,1,H,W) or an expand()ed view): ONE solve launch over the problem-major B (S + E) rows.  One grid per problem (B,1,H,W): the initial
+    trajectories are transposed once to sample-major and S + E solves of B rows each read the caller's grids -- no S-fold copy of them -- then the selection reads
+    the sample-major result.  No host copy, no synchronisation, and a sample whose system is not positive definite (or not finite) is discarded, not raised on:
+    usable inside torch.cuda.graph.  Static covariances only.  max_iters / tol_delta: optim_params' unless given.
+    -> (th_best (B,n,d), MultiStartInfo): select (SelectInfo), prior (PriorSampleInfo of the drawn samples), iters, err_final, spd_info (B, S + E)."""
+    if self.learn_module_fcn is not None:
+      raise ValueError('plan_multistart runs the fused loop with static covariances; a planner with learn modules chains the long form instead: sample_prior(), '
+                       'forward() on thb.flatten(0, 1), interpolate() and utils.planner_utils.select_samples_torch (INTEGRATION.md)')
+    from ..datasets.problem_generation import PriorSampleInfo
+    pl = self.plan_layer
+    B, S = int(startb.shape[0]), int(num_samples)
+    th, _, pflags = pl.prior_samples(startb, goalb, S, None, mean, scale, seed, first_problem)
+    dt, n, d = th.dtype, pl.num_traj_states, pl.state_dim
+    if th_extra is not None:
+      if th_extra.dim() != 4 or th_extra.shape[0] != B or tuple(th_extra.shape[2:]) != (n, d): raise ValueError('th_extra must be (%d,E,%d,%d), got %s' % (B, n, d, tuple(th_extra.shape)))
+      th = torch.cat((th, th_extra.detach().to(dt)), 1)
+    T = int(th.shape[1])
+    max_iters = int(self.optim_params['max_iters']) if max_iters is None else int(max_iters)
+    tol_delta = float(self.optim_params['tol_delta']) if tol_delta is None else float(tol_delta)
+    st, go = startb.detach().to(dt), goalb.detach().to(dt)
+    shared = sdfb.shape[0] == 1 or sdfb.stride(0) == 0
+    dev = th.device
+    if shared:
+      th0, st, go = th.reshape(B * T, n, d), st.repeat_interleave(T, 0), go.repeat_interleave(T, 0)
+      lead = (B, T)
+    else:
+      th0, st, go = th.transpose(0, 1).contiguous().view(T * B, n, d), st.repeat(T, 1, 1), go.repeat(T, 1, 1)
+      if pl.auto_tile: sdfb = pl._auto_tiled(sdfb, B)
+      lead = (T, B)
+    th_out = torch.empty_like(th0)
+    iters = torch.empty((T * B,), dtype=torch.int32, device=dev)
+    info = torch.empty((T * B,), dtype=torch.int32, device=dev)
+    ef = torch.empty((T * B,), dtype=dt, device=dev)
+    pl.solve_rows(th0, st.contiguous(), go.contiguous(), sdfb, max_iters, tol_delta, th_out, iters, ef, info, groups=1 if shared else T)
+    th_best, sel = pl.select_samples(th_out.view(lead + (n, d)), sdfb, score=ef.view(lead), exclude=info.view(lead), num_inter=num_inter, eps=eps,
+                                     require_inside=require_inside, sample_major=not shared, return_order=True)
+    pm = (lambda t: t.view(lead)) if shared else (lambda t: t.view(lead).transpose(0, 1))
+    return th_best, MultiStartInfo(sel, PriorSampleInfo(pflags), pm(iters), pm(ef), pm(info))
 
   def sample_prior(self, startb, goalb, num_samples, **kw):
     """num_samples trajectories per problem drawn from the GP prior the planner optimises under -- the start and goal priors and the constant-velocity GP factors,

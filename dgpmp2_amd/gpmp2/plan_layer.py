@@ -1450,6 +1450,83 @@ class PlanLayer(nn.Module):
     from ..datasets.problem_generation import lift_headings
     return lift_headings(self, th2b, **kw)
 
+  def select_samples(self, thb, sdfb=None, score=None, exclude=None, num_inter=7, eps=0.0, require_inside=True, env_index=None, sample_major=False, return_order=False):
+    """Multi-start selection in ONE launch (dgp_select_samples; include/dgpmp2_hip.h states the rule, utils.planner_utils.select_samples_torch is its torch mirror):
+    per problem, the GP-interpolated dense check of each of its S optimised trajectories (num_inter states per interval, epsilon eps, as interpolate()), their
+    total order -- usable and free first, then by the smallest penetration, then by score, then by index -- and the chosen trajectory gathered.  thb (B,S,n,d), or
+    (S,B,n,d) with sample_major (what S solves of B rows on per-problem grids leave behind), like score (smaller is better: err_final) and exclude (non-zero:
+    unusable -- the solve's SPD flags); sdfb: ONE GRID PER PROBLEM (B,1,H,W), a shared grid ((1,1,H,W) or an expand()ed view), a TiledSdf, or None: no collision
+    check; env_index (B,) int32: the grid of problem b among sdfb's; require_inside: a sample that leaves the limits is rejected.  Nothing is copied to the host,
+    nothing synchronises, nothing raises on a bad sample: usable inside torch.cuda.graph.  No autograd: inputs are detached.
+    -> (th_best (B,n,d), SelectInfo)."""
+    from ..utils.planner_utils import SelectInfo
+    n, d = self.num_traj_states, self.state_dim
+    if thb.dim() != 4 or thb.shape[2] != n or thb.shape[3] != d:
+      raise ValueError('thb must be (B,S,%d,%d) (or (S,B,%d,%d) with sample_major), got %s' % (n, d, n, d, tuple(thb.shape)))
+    B, S = (int(thb.shape[1]), int(thb.shape[0])) if sample_major else (int(thb.shape[0]), int(thb.shape[1]))
+    lead = (S, B) if sample_major else (B, S)
+    if S < 1 or S > _capi.DGP_MAX_SELECT_SAMPLES: raise ValueError('select_samples takes 1..%d samples per problem, got %d' % (_capi.DGP_MAX_SELECT_SAMPLES, S))
+    K = int(num_inter)
+    if K != num_inter or K < 0 or K > _capi.DGP_MAX_NUM_INTER: raise ValueError('num_inter must be an integer in 0..%d, got %r' % (_capi.DGP_MAX_NUM_INTER, num_inter))
+    dtype = thb.dtype
+    solver = self._solvers.get(dtype) or self._solver(dtype)
+    dev = thb.get_device()
+    if dev < 0: _require_cuda(thb, 'thb')
+    if sdfb is None and env_index is not None: raise ValueError('env_index names grids: it needs sdfb')
+    if sdfb is not None and (n - 1) * (K + 1) + 1 < 3: raise ValueError('the collision check needs at least 3 dense states: raise num_inter')
+    thc = thb.detach().contiguous()
+    keep = [thc]
+
+    def lead_arg(t, name, to):
+      if t is None: return None
+      _require_cuda(t, name)
+      if t.get_device() != dev: _same_device(dev, **{name: t})
+      if tuple(t.shape) != lead: raise ValueError('%s must be %s like the leading axes of thb, got %s' % (name, lead, tuple(t.shape)))
+      t = t.detach().to(to).contiguous()
+      keep.append(t)
+      return t
+    sc, ex = lead_arg(score, 'score', dtype), lead_arg(exclude, 'exclude', torch.int32)
+    ei, arg = None, None
+    if sdfb is not None:
+      G = B
+      if env_index is not None:
+        _require_cuda(env_index, 'env_index')
+        if env_index.get_device() != dev: _same_device(dev, env_index=env_index)
+        if tuple(env_index.shape) != (B,): raise ValueError('env_index must be (%d,), got %s' % (B, tuple(env_index.shape)))
+        ei = env_index.detach().to(torch.int32).contiguous()
+        G = int(sdfb.shape[0])
+      elif self.auto_tile: sdfb = self._auto_tiled(sdfb, B)
+      sd = self._sdf_args(sdfb, dtype, G, dev)
+      keep.append(sd[7])
+      arg = _capi.DgpSdf(*sd[:7])
+    device = thc.device
+    th_best = torch.empty((B, n, d), dtype=dtype, device=device)
+    best = torch.empty((B,), dtype=torch.int32, device=device)
+    status = torch.empty((B, S), dtype=torch.int32, device=device)
+    order = torch.empty((B, S), dtype=torch.int32, device=device) if return_order else None
+    sample_raw = torch.empty((B, S, _capi.DGP_DENSE_COUNT), dtype=torch.float64, device=device) if sdfb is not None else None
+    raw = torch.empty((B, _capi.DGP_SELECT_COUNT), dtype=torch.float64, device=device)
+    import ctypes
+    params = _capi.Solver.select_params(K, eps, sample_major, require_inside)
+    _launch(dev, _capi.get_api().select_samples, solver.h, B, S, thc.data_ptr(), _ptr(sc), _ptr(ex), ctypes.byref(arg) if arg is not None else None, _ptr(ei),
+            ctypes.byref(params), th_best.data_ptr(), best.data_ptr(), _ptr(order), status.data_ptr(), _ptr(sample_raw), raw.data_ptr(), _raw_stream(dev))
+    return th_best, SelectInfo(best, status, order, sample_raw, raw)
+
+  def solve_rows(self, th0, st, go, sdfb, max_iters, tol_delta, th_out, iters, err_final, info, groups=1):
+    """dgp_gn_solve on contiguous row blocks, static covariances, nothing copied to the host and nothing raised: `groups` launches of B = rows / groups
+    trajectories each, block g of every tensor against the same sdfb (one shared grid, or B grids: one per row of a block).  th0, th_out (rows,n,d); st, go
+    (rows,1,d); iters, info (rows,) int32; err_final (rows,) of th0's dtype.  The building block of DiffGPMP2Planner.plan_multistart."""
+    dtype, dev = th0.dtype, th0.get_device()
+    solver = self._solvers.get(dtype) or self._solver(dtype)
+    B = th0.shape[0] // groups
+    sd = self._sdf_args(sdfb, dtype, B, dev)
+    stream = _raw_stream(dev)
+    for g in range(groups):
+      r = slice(g * B, (g + 1) * B)
+      _launch(dev, self._pc.gn_solve, solver.h, B, th0[r].data_ptr(), st[r].data_ptr(), go[r].data_ptr(), *sd[:7], *_NO_COVS, int(max_iters), float(tol_delta),
+              th_out[r].data_ptr(), iters[r].data_ptr(), None, None, err_final[r].data_ptr(), info[r].data_ptr(), stream)
+    return sd[7]
+
   def sample_prior(self, startb, goalb, num_samples, **kw):
     """datasets.problem_generation.prior_samples(self, startb, goalb, num_samples, **kw): GP-prior trajectory samples for a multi-start -> (thb (B,S,n,d), PriorSampleInfo)."""
     from ..datasets.problem_generation import prior_samples

@@ -283,3 +283,91 @@ def heading_lift_torch(th2b, total_time_sec, start_heading=None, goal_heading=No
     thb[..., 5] = ((wN - w0) / T * 1.0).to(th2b.dtype)[:, None]
   zeros = torch.zeros(B, 1, 3, dtype=th2b.dtype, device=dev)
   return torch.cat((thb[:, :1, :3], zeros), -1), torch.cat((thb[:, N:, :3], zeros), -1), thb, turn, info
+
+
+SEL_COLLIDING, SEL_OUTSIDE, SEL_NON_FINITE, SEL_EXCLUDED = 1, 2, 4, 8      # bits of dgp_select_samples' `status`
+SELECT_NAMES = ('solved', 'num_accepted', 'best_index', 'best_score', 'best_max_penetration', 'best_status')      # columns of its problem summary
+
+
+class SelectInfo(object):
+  """What dgp_select_samples reports, device tensors (select_samples_torch: on thb's device): `best` (B,) int32 the chosen sample of every problem; `status` (B,S) int32
+  of SEL_* bits and `order` (B,S) int32, all samples best first (None unless asked for); `sample_raw` (B,S,6) float64, the dense-check summary of every sample
+  (columns _capi.DENSE_NAMES; None without grids); `raw` (B,6) float64 (columns SELECT_NAMES).  solved (bool: the chosen sample collides with nothing, stays inside
+  the limits where that is required, is finite and not excluded), num_accepted (int64), best_score, best_max_penetration and the (B,S) bool views of `status`
+  colliding, outside, non_finite, excluded are formed on access by one small torch op each."""
+  __slots__ = ('best', 'status', 'order', 'sample_raw', 'raw')
+  _COL = {name: i for i, name in enumerate(SELECT_NAMES)}
+  _BITS = {'colliding': SEL_COLLIDING, 'outside': SEL_OUTSIDE, 'non_finite': SEL_NON_FINITE, 'excluded': SEL_EXCLUDED}
+
+  def __init__(self, best, status, order, sample_raw, raw):
+    self.best, self.status, self.order, self.sample_raw, self.raw = best, status, order, sample_raw, raw
+
+  def __getattr__(self, name):
+    if name in SelectInfo.__slots__: raise AttributeError(name)
+    bit = self._BITS.get(name)
+    if bit is not None: return (self.status & bit) != 0
+    if name == 'solved': return self.raw[:, 0] != 0
+    if name == 'num_accepted': return self.raw[:, 1].to(torch.int64)
+    if name in ('best_score', 'best_max_penetration'): return self.raw[:, self._COL[name]]
+    if name == 'best_status': return self.raw[:, 5].to(torch.int64)
+    raise AttributeError(name)
+
+
+def select_samples_torch(thb, sdfb=None, score=None, exclude=None, total_time_sec=10.0, x_lims=(-5.0, 5.0), y_lims=(-5.0, 5.0), sphere_radius=0.0, num_inter=7, eps=0.0,
+                         require_inside=True, env_index=None, sample_major=False):
+  """Multi-start selection in plain torch ops on any device: the documented mirror of dgp_select_samples (include/dgpmp2_hip.h states the rule) and the definition
+  of the long form -- per problem, the GP-interpolated dense check of each of its S optimised trajectories (gp_interpolate_traj, num_inter states per interval,
+  bilinear lookup, hinge at eps + sphere_radius), the status bits, the tiers and the total order as a stable lexicographic sort, and the chosen trajectory by
+  indexing.  thb (B,S,n,d) -- (S,B,n,d) with sample_major, like score and exclude; sdfb (B | 1,1,H,W) / (B | 1,H,W) / a TiledSdf: one grid per PROBLEM, one shared
+  grid, or None (no collision check); env_index (B,): the grid of problem b.  The check runs in float64; its sums associate differently from the kernel's and its
+  dense states agree with the kernel's to rounding, so the integer results are the kernel's and the penetrations agree to rounding.
+  -> (th_best (B,n,d), SelectInfo) with status, order and sample_raw always present."""
+  from .sdf_utils import _rowmajor_grids, bilinear_interpolate_torch
+  th = thb.transpose(0, 1) if sample_major else thb
+  B, S, n, d = th.shape
+  dev = th.device
+  pm = lambda t: (t.transpose(0, 1) if sample_major else t)
+  sc = torch.zeros((B, S), dtype=torch.float64, device=dev) if score is None else pm(score).to(torch.float64)
+  ex = torch.zeros((B, S), dtype=torch.bool, device=dev) if exclude is None else pm(exclude) != 0
+  K = int(num_inter)
+  dense = gp_interpolate_traj(th.reshape(B * S, n, d).to(torch.float64), total_time_sec, n - 1, K)      # (B S, N_d, d)
+  nd = dense.shape[1]
+  x, y = dense[:, :, 0], dense[:, :, 1]
+  inside = (x >= float(x_lims[0])) & (x <= float(x_lims[1])) & (y >= float(y_lims[0])) & (y <= float(y_lims[1]))      # a NaN is outside
+  outside = (~inside).any(1).view(B, S)
+  sample_raw = None
+  max_pen = torch.zeros((B, S), dtype=torch.float64, device=dev)
+  colliding = torch.zeros((B, S), dtype=torch.bool, device=dev)
+  if sdfb is not None:
+    if nd < 3: raise ValueError('the collision check needs at least 3 dense states, got %d' % nd)
+    g = _rowmajor_grids(sdfb).to(torch.float64)
+    if env_index is not None: g = g.index_select(0, env_index.to(torch.int64))
+    if g.shape[0] not in (1, B): raise ValueError('sdfb has %d grids for %d problems' % (g.shape[0], B))
+    res = (float(x_lims[1]) - float(x_lims[0])) / g.shape[-1]
+    dist = bilinear_interpolate_torch(g, dense[:, :, :2].reshape(B, S * nd, 2), res, x_lims, y_lims)[0].view(B, S, nd)
+    tot = float(eps) + float(sphere_radius)
+    cost = torch.where(dist <= tot, tot - dist, torch.zeros_like(dist))
+    inner = cost[:, :, 1:-1]
+    hit = inner != 0
+    cnt = hit.sum(-1)
+    nan = torch.isnan(inner)
+    neg = torch.full_like(inner, float('-inf'))
+    worst = torch.where(nan.any(-1), torch.argmax(nan.to(torch.int8), -1), torch.argmax(torch.where(nan, neg, inner), -1)) + 1
+    max_pen = torch.where(nan.any(-1), torch.full_like(inner[..., 0], float('nan')), inner.max(-1)[0])
+    first = torch.where(cnt > 0, torch.argmax(hit.to(torch.int8), -1) + 1, torch.full_like(cnt, -1))
+    sample_raw = torch.stack(((cnt > 0).to(torch.float64), cnt.to(torch.float64), inner.mean(-1), max_pen, first.to(torch.float64), worst.to(torch.float64)), -1)
+    colliding = cnt != 0
+  non_finite = ~torch.isfinite(th.reshape(B, S, -1)).all(-1) | ~torch.isfinite(sc) | torch.isnan(max_pen)
+  status = (colliding.to(torch.int32) * SEL_COLLIDING + outside.to(torch.int32) * SEL_OUTSIDE + non_finite.to(torch.int32) * SEL_NON_FINITE + ex.to(torch.int32) * SEL_EXCLUDED)
+  two, one, zero = torch.full_like(status, 2), torch.full_like(status, 1), torch.zeros_like(status)
+  tier = torch.where(non_finite | ex, two, torch.where(colliding | (outside if require_inside else torch.zeros_like(outside)), one, zero))
+  # the total order as a stable lexicographic sort, least significant key first: (index,) score, penetration, tier
+  zf = torch.zeros_like(sc)
+  order = torch.arange(S, device=dev).expand(B, S)
+  for key in (torch.where(tier < 2, sc, zf) + 0.0, torch.where(tier == 1, max_pen, zf) + 0.0, tier):      # (+ 0.0: -0.0 and 0.0 tie)
+    order = order.gather(1, torch.sort(key.gather(1, order), dim=1, stable=True)[1])
+  best = order[:, 0]
+  rows = torch.arange(B, device=dev)
+  raw = torch.stack(((tier[rows, best] == 0).to(torch.float64), (tier == 0).sum(1).to(torch.float64), best.to(torch.float64), sc[rows, best], max_pen[rows, best],
+                     status[rows, best].to(torch.float64)), -1)
+  return th[rows, best].clone(), SelectInfo(best.to(torch.int32), status, order.to(torch.int32), sample_raw, raw)

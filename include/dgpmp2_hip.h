@@ -836,6 +836,73 @@ int dgp_heading_lift(const DgpHandle* h /* dof 3 */, int32_t batch, const DgpHea
                      double* turns_out, int32_t* info,                          /* (B,n), (B); each may be NULL */
                      void* stream);
 
+/* Multi-start selection, ONE launch: per problem, the dense collision check of each of its num_samples optimised trajectories, their total order, and the chosen
+ * one gathered -- the back half of dgp_prior_samples -> dgp_gn_solve over the B S rows.  No counterpart in the reference, which optimises one trajectory per problem.
+ * Inputs.  th: the optimised samples, io_dtype, (B,S,n,d) -- or (S,B,n,d) with sample_major, what S solve launches of B rows on per-problem grids leave behind;
+ *   score (B,S) / (S,B) io_dtype or NULL (= all 0.0): smaller is better (err_final of dgp_gn_solve);  exclude (B,S) / (S,B) int32 or NULL: non-zero = unusable (info of
+ *   dgp_gn_solve; bit 1 of dgp_prior_samples' info);  sdf as for dgp_gp_interpolate, batch_stride the distance between PROBLEMS' grids (0 = one shared grid), or
+ *   NULL: no collision check;  env_index (B) int32 or NULL, as for dgp_sample_problems: problem b reads grid env_index[b] (NULL: grid b); needs sdf.
+ * The dense check of a sample is dgp_gp_interpolate's, on the same N_d = (n - 1)(K + 1) + 1 dense states, K = num_inter: the same closed form and operation order, every
+ *   dense state looked up at its unrounded fp64 position with epsilon eps, the same six numbers over dense states 1 .. N_d - 2, reduced by the same lanes in the same
+ *   order.  sample_summary[b, s] is BIT FOR BIT what dgp_gp_interpolate(..., summary) returns for that trajectory on that grid, AVG_PENETRATION included.
+ * Status bits of a sample (status (B,S), always problem-major like order and sample_summary):
+ *   DGP_SEL_COLLIDING   NUM_COLLIDING != 0.  Never set without sdf.
+ *   DGP_SEL_OUTSIDE     the position of ANY dense state 0 .. N_d - 1, the two end states included, lies outside the handle's closed [x_min, x_max] x [y_min, y_max]
+ *                       (a NaN is outside): the rule of dgp_prior_samples' info bit 0 on the position the lookup takes.  Computed with or without sdf.
+ *   DGP_SEL_NON_FINITE  one of the sample's n d stored values or its score is not finite, or MAX_PENETRATION is NaN.
+ *   DGP_SEL_EXCLUDED    exclude != 0.
+ * Tiers.  2: NON_FINITE or EXCLUDED.  0: not tier 2, not COLLIDING and not (require_inside and OUTSIDE).  1: the rest -- usable trajectories that collide or leave the map.
+ * Total order.  Sample s precedes sample t iff, in turn: its tier is smaller; then, in tier 1 only, its MAX_PENETRATION is smaller (0 for every sample without sdf);
+ *   then, in tiers 0 and 1, its score converted to double is smaller by `<` (-0.0 and 0.0 tie); then its index s is smaller.  Every key is an input or a bit-exact
+ *   intermediate: the order is exact.  order[b] is that permutation of 0 .. S - 1, best first; best[b] = order[b][0].
+ * th_best[b] (n,d) is a BIT COPY of the chosen trajectory: NaN payloads and -0.0 included, no arithmetic touches it (it moves as 16- / 8- / 4-byte words, whichever the
+ *   addresses allow: pointers need only be aligned to their element type).
+ * problem_summary (B, DGP_SELECT_COUNT) doubles: SOLVED 1.0 iff the chosen sample is of tier 0; NUM_ACCEPTED the number of tier-0 samples; BEST_INDEX; BEST_SCORE (as a
+ *   double; 0.0 without score); BEST_MAX_PENETRATION (0.0 without sdf); BEST_STATUS the chosen sample's status bits.
+ * Outputs: each may be NULL, not all six.  sample_summary needs sdf.
+ * DGP_EINVAL, nothing launched: a NULL handle, th or p; a wrong struct_size; batch < 1; num_samples outside 1 .. 1024, or batch * num_samples >= 2^31; num_inter outside
+ *   0 .. 1023; eps not finite; every output NULL; sample_summary or env_index without sdf (or without sdf->data); sdf given and N_d < 3.
+ * Every num_states, both dof and both io_dtype a handle accepts are accepted (the heading of the dof 3 robot is a column like any other); row-major and DGP_SDF_TILED4
+ * grids.  One workgroup per problem, the keys of its samples in LDS: one launch, no atomics, nothing allocated, copied or synchronised -- capturable in a HIP graph;
+ * bit-identical from run to run, for either layout of th, either grid layout and wherever the problem sits in the batch. */
+#define DGP_SEL_COLLIDING   1
+#define DGP_SEL_OUTSIDE     2
+#define DGP_SEL_NON_FINITE  4
+#define DGP_SEL_EXCLUDED    8
+#define DGP_SELECT_SOLVED               0
+#define DGP_SELECT_NUM_ACCEPTED         1
+#define DGP_SELECT_BEST_INDEX           2
+#define DGP_SELECT_BEST_SCORE           3
+#define DGP_SELECT_BEST_MAX_PENETRATION 4
+#define DGP_SELECT_BEST_STATUS          5
+#define DGP_SELECT_COUNT                6
+typedef struct DgpSelectParams {
+  uint32_t struct_size;     /* = sizeof(DgpSelectParams) */
+  int32_t  num_inter;       /* K of the dense check, 0 .. 1023, as dgp_gp_interpolate */
+  double   eps;             /* epsilon of the dense check's hinge, as dgp_gp_interpolate */
+  int32_t  sample_major;    /* 0: th (B,S,n,d), score / exclude (B,S);  1: th (S,B,n,d), score / exclude (S,B) */
+  int32_t  require_inside;  /* non-zero: DGP_SEL_OUTSIDE rejects a sample (tier 1) */
+} DgpSelectParams;          /* 24 bytes */
+int dgp_select_samples(const DgpHandle* h, int32_t batch, int32_t num_samples,
+                       const void* th,             /* optimised samples, io_dtype */
+                       const void* score,          /* io_dtype or NULL */
+                       const int32_t* exclude,     /* int32 or NULL */
+                       const DgpSdf* sdf,          /* or NULL: no collision check */
+                       const int32_t* env_index,   /* (B) or NULL */
+                       const DgpSelectParams* p,
+                       void* th_best,              /* (B,n,d) io_dtype */
+                       int32_t* best,              /* (B) */
+                       int32_t* order,             /* (B,S) */
+                       int32_t* status,            /* (B,S) */
+                       double* sample_summary,     /* (B,S,DGP_DENSE_COUNT) */
+                       double* problem_summary,    /* (B,DGP_SELECT_COUNT) */
+                       void* stream);
+/* What dgp_select_samples launches for num_samples samples checked with num_inter interpolated states (the function its dispatch itself reads): lanes per trajectory
+ * (16 / 32 / 64, from N_d as for dgp_gp_interpolate), wavefronts of a problem's workgroup (up to 16) and the passes in which the workgroup walks the samples.  Any
+ * pointer may be NULL.  No effect on any result. */
+int dgp_select_launch_shape(const DgpHandle* h, int32_t num_samples, int32_t num_inter,
+                            int32_t* lanes_per_traj, int32_t* waves_per_group, int32_t* passes);
+
 /* Measurement aid (no counterpart in the reference): the NEXT kernel launched by the calling thread through any entry point
  * above records its own begin and end on the two HIP events (hipEvent_t, created with timing enabled, cast to void*), the way
  * hipExtLaunchKernelGGL does -- hipEventElapsedTime(start, stop) is then that kernel's execution time, the quantity
