@@ -1,12 +1,13 @@
 // dgp_dense_walk.h -- the dense check of one trajectory by the LPT lanes of its group, stated once for gp_interpolate.hip (dgp_gp_interpolate) and
 // select_samples.hip (dgp_select_samples): the per-lane strided walk over the dense index m = lane + k LPT -- the header's closed form and operation order, the
 // obstacle lookup (gn_lane.h's obstacle_eval) at the UNROUNDED fp64 position, the lane's partial sum / maximum with its index / count / first index -- and the four
-// butterfly reductions over the group.  The order of every addition and comparison depends on N_d and LPT only, so both units give the same bits for a trajectory.
-// HIP only (the __shfl_xor butterflies); include after DGP_TL is defined.
+// butterfly reductions over the group (dgp_group.h's, and the maximum with its index below).  The order of every addition and comparison depends on N_d and LPT
+// only, so both units give the same bits for a trajectory.  HIP only (the __shfl_xor butterflies); include after DGP_TL is defined.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "gn_lane.h"
+#include "dgp_group.h"
 #include "dgp_status.h"      // (include/dgpmp2_hip.h: DGP_DENSE_*)
 
 #pragma clang fp contract(off)
@@ -15,27 +16,10 @@ namespace dgp_dense {
 
 constexpr int NO_INDEX = 0x7fffffff;
 
-template <int LPT>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-template <int LPT>
-__device__ __forceinline__ int group_sum_i(int v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-template <int LPT>
-__device__ __forceinline__ int group_min_i(int v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) {
-    const int o = __shfl_xor(v, m);
-    v = o < v ? o : v;
-  }
-  return v;
-}
+using dgp_group::group_sum;
+using dgp_group::group_sum_i;
+using dgp_group::group_min_i;
+
 // the maximum with its index: a NaN wins over every number (torch.max), the smaller index wins between equals (and between NaNs).
 // Symmetric: both partners of an exchange end with the same pair.
 template <int LPT>

@@ -36,11 +36,9 @@ inline bool is_long(int n) { return n > kMaxStates; }
 inline bool shape_supported(int lpt, int c) { return (lpt == 16 || lpt == 32 || lpt == 64) && (c == 1 || c == 2 || c == 4); }
 
 // dgp_gp_interpolate (gp_interpolate.hip): at most kMaxNumInter interpolated states per interval; N_d = (n - 1)(K + 1) + 1 dense states (at most 1023 * 1024 + 1);
-// lanes per trajectory from N_d -- the lanes walk the DENSE index -- at the thresholds of the metrics kernel: every lane has up to four dense states before a
-// wider group pays (one round of memory latency either way, traj_metrics.hip).
+// lanes per trajectory from N_d -- the lanes walk the DENSE index -- by the rule of the metrics kernel (dgp_group::lanes_for).
 constexpr int kMaxNumInter = 1023;
 inline int dense_states(int n, int num_inter) { return (n - 1) * (num_inter + 1) + 1; }
-inline int dense_lpt(int nd) { return nd <= 64 ? 16 : (nd <= 128 ? 32 : 64); }
 
 // Pick (LPT, C) for n states and a batch of B trajectories: the cheapest supported shape under a two-parameter timing model
 // fitted to profiles/tools/shape_grid.py on MI355X (static-covariance kernels, steady clocks):
@@ -355,11 +353,8 @@ inline int fill_call(const DgpHandle* h, int32_t batch, const void* th, const vo
   p.B = batch;
   p.th = th; p.start = start; p.goal = goal;
   p.sdf = sdf->data; p.sdf_rows = sdf->rows; p.sdf_cols = sdf->cols; p.sdf_bstride = sdf->batch_stride; p.sdf_layout = sdf->layout;
-  // obstacle_cost.py:34 and sdf_utils.py:57-58, evaluated exactly as Python does (fp64)
-  p.res = (h->cfg.x_lims[1] - h->cfg.x_lims[0]) / (double)sdf->cols;
+  grid_geometry(h->cfg.x_lims, h->cfg.y_lims, sdf->cols, p.res, p.orig_px, p.orig_py);
   p.inv_res = 1.0 / p.res;
-  p.orig_px = (0. - h->cfg.x_lims[0] / p.res);
-  p.orig_py = (0. - h->cfg.y_lims[0] / p.res);
   p.qc_mode = DGP_QC_STATIC; p.qc = nullptr; p.obs_w = nullptr; p.eps = nullptr;
   p.vec_mu = (aligned16(start) && aligned16(goal)) ? 1 : 0;
   if (covs) {

@@ -7,7 +7,7 @@
 // one rule serves every covariance mode.  include/dgpmp2_hip.h states the closed form and its operation order, tests/interp_oracle.py restates it, and the kernel is held
 // against that bit for bit.
 //
-// Mapping: LPT = 16 / 32 / 64 lanes per trajectory, chosen from the number of DENSE states N_d = (n - 1)(K + 1) + 1 (dgp_host::dense_lpt), 64 / LPT trajectories per
+// Mapping: LPT = 16 / 32 / 64 lanes per trajectory, chosen from the number of DENSE states N_d = (n - 1)(K + 1) + 1 (dgp_group::lanes_for), 64 / LPT trajectories per
 // wavefront.  The lanes of a trajectory walk the dense index in a strided loop, m = lane + k LPT: adjacent lanes store adjacent rows of th_dense and adjacent entries of
 // dense_cost (coalesced runs) and read the same or neighbouring support rows i = m / (K + 1), i + 1 -- the lines are in flight or in the vector L1 already, as for the
 // neighbour rows of traj_metrics.hip.  Row i + 1 is clamped to n - 1 for the load (unconditional loads); the copy rule (offset 0 is a bit copy of row i) leaves the
@@ -68,15 +68,6 @@ __global__ void __launch_bounds__(64) gp_interpolate_kernel(const InterpArgs a) 
   if (on && l < DGP_DENSE_COUNT) a.summary[b * DGP_DENSE_COUNT + l] = out;
 }
 
-template <int DOF, typename IO>
-hipError_t launch_lpt(int lpt, const InterpArgs& a, hipStream_t s, const dgp_dev::Events& ev) {
-  const int tpw = 64 / lpt;
-  const dim3 grid((unsigned)((a.p.B + tpw - 1) / tpw)), block(64);
-  if (lpt == 16) return dgp_dev::launch(gp_interpolate_kernel<DOF, IO, 16>, grid, block, 0, s, ev, a);
-  if (lpt == 32) return dgp_dev::launch(gp_interpolate_kernel<DOF, IO, 32>, grid, block, 0, s, ev, a);
-  return dgp_dev::launch(gp_interpolate_kernel<DOF, IO, 64>, grid, block, 0, s, ev, a);
-}
-
 }  // namespace
 
 extern "C" int dgp_gp_interpolate(const DgpHandle* h, int32_t batch, const void* th, int32_t num_inter, const DgpSdf* sdf, double eps,
@@ -93,10 +84,11 @@ extern "C" int dgp_gp_interpolate(const DgpHandle* h, int32_t batch, const void*
   a.nd = dgp_host::dense_states(a.p.n, num_inter);
   if (summary && a.nd < 3) return fail(DGP_EINVAL, "dgp_gp_interpolate: the summary needs at least 3 dense states (no interior state), got %d", a.nd);
   a.th_dense = th_dense; a.dense_cost = dense_cost; a.summary = summary; a.eps = eps;
-  const int lpt = dgp_host::dense_lpt(a.nd);
+  const int lpt = dgp_group::lanes_for(a.nd), tpw = 64 / lpt;
+  const dim3 grid((unsigned)((a.p.B + tpw - 1) / tpw)), block(64);
   hipStream_t s = (hipStream_t)stream;
-  const bool f64 = h->cfg.io_dtype == DGP_F64;
-  const hipError_t e = h->cfg.dof == 2 ? (f64 ? launch_lpt<2, double>(lpt, a, s, ev) : launch_lpt<2, float>(lpt, a, s, ev))
-                                       : (f64 ? launch_lpt<3, double>(lpt, a, s, ev) : launch_lpt<3, float>(lpt, a, s, ev));
+  const hipError_t e = dgp_dev::with_dof_io(h->cfg.dof, h->cfg.io_dtype == DGP_F64, [&](auto dof, auto io) {
+    return dgp_dev::with_lpt(lpt, [&](auto L) { return dgp_dev::launch(gp_interpolate_kernel<dof, decltype(io), L>, grid, block, 0, s, ev, a); });
+  });
   return dgp_dev::hip_rc(e, "dgp_gp_interpolate");
 }

@@ -18,6 +18,8 @@
 #include "dgp_prior.h"
 #include "dgp_launch.h"
 #include "dgp_philox.h"
+#include "dgp_group.h"
+#include "dgp_rowio.h"
 
 #pragma clang fp contract(off)
 
@@ -43,15 +45,9 @@ struct LiftArgs {
   int32_t vec_in, vec_out;                      // th2 / th allow the vector accesses of load_row / store_row
 };
 
-template <int LPT>
-__device__ __forceinline__ double group_scan(double x, int l) {
-#pragma unroll
-  for (int off = 1; off < LPT; off <<= 1) {
-    const double lo = __shfl_up(x, off, LPT);
-    x = l >= off ? lo + x : x;
-  }
-  return x;
-}
+using dgp_group::group_scan;
+using dgp_rowio::load_row;
+using dgp_rowio::store_row;
 
 template <int LPT>
 __device__ __forceinline__ int group_max_scan(int x, int l) {
@@ -61,38 +57,6 @@ __device__ __forceinline__ int group_max_scan(int x, int l) {
     x = (l >= off && lo > x) ? lo : x;
   }
   return x;
-}
-
-template <typename IO>
-__device__ __forceinline__ void load_row(const IO* src, IO (&v)[4], bool vec) {
-  if (vec) {
-    if constexpr (sizeof(IO) == 4) {
-      const float4 q = *reinterpret_cast<const float4*>(src);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-      const double2 q0 = *reinterpret_cast<const double2*>(src), q1 = *reinterpret_cast<const double2*>(src + 2);
-      v[0] = q0.x; v[1] = q0.y; v[2] = q1.x; v[3] = q1.y;
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = src[c];
-  }
-}
-
-template <typename IO>
-__device__ __forceinline__ void store_row(IO* dst, const IO (&v)[6], bool vec) {
-  if (vec) {
-    if constexpr (sizeof(IO) == 4) {
-#pragma unroll
-      for (int c = 0; c < 6; c += 2) *reinterpret_cast<float2*>(dst + c) = make_float2(v[c], v[c + 1]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 6; c += 2) *reinterpret_cast<double2*>(dst + c) = make_double2(v[c], v[c + 1]);
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) dst[c] = v[c];
-  }
 }
 
 __device__ __forceinline__ bool finite(double v) { return v - v == 0.0; }
@@ -174,7 +138,7 @@ __global__ void __launch_bounds__(64) heading_lift_kernel(const LiftArgs a) {
       const int st = k0 + l, sr = st <= N ? st : N;      // (lanes past the last state: row N again; their values reach no stored state)
       const bool live = st <= N;
       IO q[4];
-      load_row<IO>(src + (int64_t)sr * 4, q, a.vec_in != 0);
+      load_row<IO, 4>(src + (int64_t)sr * 4, q, a.vec_in != 0);
       const double x = (double)q[0], y = (double)q[1];
       // t_i = p_hi - p_lo, lo = max(i - 1, 0), hi = min(i + 1, N)
       double xp = __shfl_up(x, 1, LPT), yp = __shfl_up(y, 1, LPT);
@@ -261,7 +225,7 @@ __global__ void __launch_bounds__(64) heading_lift_kernel(const LiftArgs a) {
       }
       if (live) {
         if (on) {
-          store_row<IO>(dst + (int64_t)st * 6, o, a.vec_out != 0);
+          store_row<IO, 6>(dst + (int64_t)st * 6, o, a.vec_out != 0);
           if (a.turns_out != nullptr) a.turns_out[b * (int64_t)n + st] = turn;
           if (st == 0 || st == N) {
             IO* e = (IO*)(st == 0 ? a.start : a.goal) + b * 6;
@@ -289,9 +253,7 @@ hipError_t launch_n(const LiftArgs& a, hipStream_t s, const dgp_dev::Events& ev)
   const int tpw = 64 / sh.lpt;
   const dim3 grid((unsigned)((a.B + tpw - 1) / tpw)), block(64);
   if (sh.blocks > 1) return dgp_dev::launch(heading_lift_kernel<IO, 64, true>, grid, block, 0, s, ev, a);
-  if (sh.lpt == 16) return dgp_dev::launch(heading_lift_kernel<IO, 16, false>, grid, block, 0, s, ev, a);
-  if (sh.lpt == 32) return dgp_dev::launch(heading_lift_kernel<IO, 32, false>, grid, block, 0, s, ev, a);
-  return dgp_dev::launch(heading_lift_kernel<IO, 64, false>, grid, block, 0, s, ev, a);
+  return dgp_dev::with_lpt(sh.lpt, [&](auto L) { return dgp_dev::launch(heading_lift_kernel<IO, L, false>, grid, block, 0, s, ev, a); });
 }
 
 }  // namespace

@@ -286,18 +286,10 @@ extern "C" int dgp_init_paths(const DgpHandle* h, int32_t batch, const DgpSdf* s
                               const void* goal, void* th_init, uint32_t* field, int32_t* path_cells, int32_t* num_cells, double* length, int32_t* info,
                               void* stream) {
   const dgp_dev::Events ev = dgp_dev::take_events();
-  if (!h) return fail(DGP_EINVAL, "null handle");
-  const DgpConfig& c = *reinterpret_cast<const DgpConfig*>(h);      // DgpHandle's first member (dgp_host.h holds that with a static_assert); this unit needs nothing else of it
-  if (c.dof != 2) return fail(DGP_EINVAL, "dgp_init_paths: only dof == 2 (2-D point-robot problems), got %d", c.dof);
-  if (!p) return fail(DGP_EINVAL, "dgp_init_paths: null DgpPathParams");
-  if (!sdf || !sdf->data) return fail(DGP_EINVAL, "dgp_init_paths: sdf must be non-null");
-  if (!start || !goal || !th_init || !field) return fail(DGP_EINVAL, "dgp_init_paths: start, goal, th_init and field must be non-null device pointers");
-  if (batch < 1) return fail(DGP_EINVAL, "dgp_init_paths: batch must be positive, got %d", batch);
-  if (sdf->layout == DGP_SDF_TILED4) return fail(DGP_EINVAL, "dgp_init_paths: tiled grids (DGP_SDF_TILED4) are not implemented here: pass the row-major grid");
-  if (sdf->layout != DGP_SDF_ROWMAJOR) return fail(DGP_EINVAL, "dgp_init_paths: bad DgpSdf::layout %d", sdf->layout);
-  if (sdf->rows < 1 || sdf->cols < 1 || sdf->rows > MAX_SIDE || sdf->cols > MAX_SIDE)
-    return fail(DGP_EINVAL, "dgp_init_paths: grid sides must be in 1..%d, got %dx%d", MAX_SIDE, sdf->rows, sdf->cols);
-  if (sdf->batch_stride < 0) return fail(DGP_EINVAL, "dgp_init_paths: negative sdf batch stride");
+  dgp_dev::RowMajorGrid g;
+  const int rc = dgp_dev::rowmajor_grid("dgp_init_paths", h, batch, sdf, p, "DgpPathParams", start && goal && th_init && field, "start, goal, th_init and field", MAX_SIDE, g);
+  if (rc != DGP_OK) return rc;
+  const DgpConfig& c = *g.cfg;
   if (p->max_sweeps < 1 || p->max_sweeps > 4096) return fail(DGP_EINVAL, "dgp_init_paths: max_sweeps must be in 1..4096, got %d", p->max_sweeps);
   if (p->path_cap < 0) return fail(DGP_EINVAL, "dgp_init_paths: path_cap must be >= 0, got %d", p->path_cap);
   if (!(p->clearance == p->clearance)) return fail(DGP_EINVAL, "dgp_init_paths: NaN clearance");
@@ -306,9 +298,7 @@ extern "C" int dgp_init_paths(const DgpHandle* h, int32_t batch, const DgpSdf* s
   a.env_index = env_index; a.start = start; a.goal = goal; a.th_init = th_init; a.field = field;
   a.path_cells = path_cells; a.num_cells = num_cells; a.info = info; a.length = length;
   a.clearance = p->clearance;
-  a.res = (c.x_lims[1] - c.x_lims[0]) / (double)sdf->cols;      // the lookup's (dgp_host::fill_call)
-  a.orig_x = (0. - c.x_lims[0] / a.res);
-  a.orig_y = (0. - c.y_lims[0] / a.res);
+  a.res = g.res; a.orig_x = g.orig_x; a.orig_y = g.orig_y;
   a.total_time_sec = c.total_time_sec;
   a.max_sweeps = p->max_sweeps; a.path_cap = p->path_cap;
   const dim3 grid((unsigned)batch), block(64);

@@ -22,6 +22,8 @@
 #include "dgp_prior.h"
 #include "dgp_launch.h"
 #include "dgp_philox.h"
+#include "dgp_group.h"
+#include "dgp_rowio.h"
 
 #pragma clang fp contract(off)
 
@@ -72,16 +74,8 @@ __device__ __forceinline__ void noise_row(const PriorArgs& a, const double* nz, 
   }
 }
 
-// inclusive Hillis-Steele scan over the LPT lanes of a group: x_l <- x_(l - off) + x_l for l >= off, off = 1, 2, 4, ...
-template <int LPT>
-__device__ __forceinline__ double group_scan(double x, int l) {
-#pragma unroll
-  for (int off = 1; off < LPT; off <<= 1) {
-    const double lo = __shfl_up(x, off, LPT);
-    x = l >= off ? lo + x : x;
-  }
-  return x;
-}
+using dgp_group::group_scan;
+using dgp_rowio::store_row;
 
 // W(t) g = P(t) Phi(t_end - t)^T g, g = S^-1 (an observation residual)
 template <int DOF>
@@ -116,24 +110,6 @@ __device__ __forceinline__ void group_mat_vec(const double* M, const double (&x)
   for (int j = 1; j < D; ++j) s = s + row[j] * x[j];
 #pragma unroll
   for (int i = 0; i < D; ++i) y[i] = __shfl(s, gbase + i);
-}
-
-template <typename IO, int D>
-__device__ __forceinline__ void store_row(IO* dst, const IO (&v)[D], bool vec) {
-  if (vec) {
-    if constexpr (sizeof(IO) == 4 && D == 4) {
-      *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-    } else if constexpr (sizeof(IO) == 4) {
-#pragma unroll
-      for (int c = 0; c < D; c += 2) *reinterpret_cast<float2*>(dst + c) = make_float2(v[c], v[c + 1]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < D; c += 2) *reinterpret_cast<double2*>(dst + c) = make_double2(v[c], v[c + 1]);
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < D; ++c) dst[c] = v[c];
-  }
 }
 
 // The unconditioned chain over one block of LPT states starting at state k0: lane l gets x_(k0 + l) in (xp, xv) and its noise row in z.  carry_p / carry_v: the
@@ -274,9 +250,7 @@ hipError_t launch_n(const PriorArgs& a, hipStream_t s, const dgp_dev::Events& ev
   const int tpw = 64 / sh.lpt;
   const dim3 grid((unsigned)((a.T + tpw - 1) / tpw)), block(64);
   if (sh.blocks > 1) return dgp_dev::launch(prior_samples_kernel<DOF, IO, 64, true>, grid, block, 0, s, ev, a);
-  if (sh.lpt == 16) return dgp_dev::launch(prior_samples_kernel<DOF, IO, 16, false>, grid, block, 0, s, ev, a);
-  if (sh.lpt == 32) return dgp_dev::launch(prior_samples_kernel<DOF, IO, 32, false>, grid, block, 0, s, ev, a);
-  return dgp_dev::launch(prior_samples_kernel<DOF, IO, 64, false>, grid, block, 0, s, ev, a);
+  return dgp_dev::with_lpt(sh.lpt, [&](auto L) { return dgp_dev::launch(prior_samples_kernel<DOF, IO, L, false>, grid, block, 0, s, ev, a); });
 }
 
 }  // namespace
@@ -307,7 +281,7 @@ extern "C" int dgp_prior_samples(const DgpHandle* h, int32_t batch, int32_t num_
   const uintptr_t need = (f64 || c.dof == 2) ? 15u : 7u;      // rows of 16 / 32 / 48 bytes move as 16-byte vectors, the 24-byte rows of dof 3 fp32 as 8-byte ones
   a.vec = (reinterpret_cast<uintptr_t>(th) & need) == 0 ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
-  const hipError_t e = c.dof == 2 ? (f64 ? launch_n<2, double>(a, s, ev) : launch_n<2, float>(a, s, ev)) : (f64 ? launch_n<3, double>(a, s, ev) : launch_n<3, float>(a, s, ev));
+  const hipError_t e = dgp_dev::with_dof_io(c.dof, f64, [&](auto dof, auto io) { return launch_n<dof, decltype(io)>(a, s, ev); });
   return dgp_dev::hip_rc(e, "dgp_prior_samples");
 }
 

@@ -6,7 +6,7 @@
 // (obstacle_finish folds eps + radius and the `<=` selection in), and the closed-form gradient.  include/dgpmp2_hip.h states both operation orders,
 // tests/lookup_oracle.py restates them, and the kernels are held against that bit for bit.  DGP_TL = 2 (this unit's flag): the grid layout is a run-time branch.
 //
-// Forward mapping: LPT = 16 / 32 / 64 lanes per batch row, chosen from S (dgp_host::dense_lpt), 64 / LPT rows per wavefront.  The lanes of a row walk its points in
+// Forward mapping: LPT = 16 / 32 / 64 lanes per batch row, chosen from S (dgp_group::lanes_for), 64 / LPT rows per wavefront.  The lanes of a row walk its points in
 // a strided loop, i = lane + k LPT: adjacent lanes read adjacent point rows and store adjacent d_obs / J entries.  A point row moves as ONE vector of two elements
 // (8 bytes fp32, 16 bytes fp64) when point_stride == 2 and points / J are aligned to it, element by element otherwise: the access width is the only difference.
 // Summary: every lane keeps a count, a first index and a minimum with its index over the fp64 distances of its points, then fixed-order butterflies over the row's
@@ -23,6 +23,7 @@
 #endif
 #include "dgp_host.h"
 #include "dgp_launch.h"
+#include "dgp_group.h"
 
 #pragma clang fp contract(off)
 
@@ -87,6 +88,7 @@ __device__ __forceinline__ void cell_of(const dgp::GnParams& p, const IO* __rest
 // -0: harmless under the hinge of the step kernels; here J and the gradients are held to the reference bit for bit, and a clamped cell gives J = -0.0)
 __device__ __forceinline__ double quot_res(const dgp::GnParams& p, double u) { return u == 0.0 ? u : dgp::div_res(p, u); }
 
+// (dgp_rowio.h's rule at D = 2; not its load_row / store_row: through HIP's float2 / double2 both kernels here compile to other code than through these vectors)
 template <typename IO, bool VEC>
 __device__ __forceinline__ void load_pair(const IO* p, IO& x, IO& y) {
   if (VEC) {
@@ -109,21 +111,9 @@ __device__ __forceinline__ void store_pair(IO* p, IO x, IO y) {
   }
 }
 
-template <int LPT>
-__device__ __forceinline__ int group_sum_i(int v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-template <int LPT>
-__device__ __forceinline__ int group_min_i(int v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) {
-    const int o = __shfl_xor(v, m);
-    v = o < v ? o : v;
-  }
-  return v;
-}
+using dgp_group::group_sum_i;
+using dgp_group::group_min_i;
+
 // the minimum with its index: a NaN wins over every number (torch.min), the smaller index wins between equals (and between NaNs).
 // Symmetric: both partners of an exchange end with the same pair.  A lane without a point carries (+inf, NO_INDEX) and loses every tie.
 template <int LPT>
@@ -243,15 +233,13 @@ template <typename IO, bool VEC>
 hipError_t launch_fwd(int lpt, const LookupArgs& a, hipStream_t s, const dgp_dev::Events& ev) {
   const int tpw = 64 / lpt;
   const dim3 grid((unsigned)(((int64_t)a.p.B + tpw - 1) / tpw)), block(64);
-  if (lpt == 16) return dgp_dev::launch(sdf_lookup_kernel<IO, 16, VEC>, grid, block, 0, s, ev, a);
-  if (lpt == 32) return dgp_dev::launch(sdf_lookup_kernel<IO, 32, VEC>, grid, block, 0, s, ev, a);
-  return dgp_dev::launch(sdf_lookup_kernel<IO, 64, VEC>, grid, block, 0, s, ev, a);
+  return dgp_dev::with_lpt(lpt, [&](auto L) { return dgp_dev::launch(sdf_lookup_kernel<IO, L, VEC>, grid, block, 0, s, ev, a); });
 }
 
 template <typename IO>
 hipError_t launch_fwd_io(const LookupArgs& a, hipStream_t s, const dgp_dev::Events& ev) {
   const bool vec = a.pstride == 2 && aligned(a.points, 2 * sizeof(IO)) && aligned(a.J, 2 * sizeof(IO));
-  const int lpt = dgp_host::dense_lpt(a.S);
+  const int lpt = dgp_group::lanes_for(a.S);
   return vec ? launch_fwd<IO, true>(lpt, a, s, ev) : launch_fwd<IO, false>(lpt, a, s, ev);
 }
 

@@ -5,7 +5,7 @@
 // dgp_gn_solve over the B S rows; this unit decides, per problem, which optimised sample to keep.  include/dgpmp2_hip.h states the rule (status bits, tiers, the
 // total order), tests/select_oracle.py restates it, and the kernel is held against that exactly: every key of the order is an input or a bit-exact intermediate.
 //
-// Mapping: one workgroup per problem.  A sample occupies a group of LPT = 16 / 32 / 64 lanes (dgp_host::dense_lpt(N_d), as dgp_gp_interpolate), 64 / LPT samples per
+// Mapping: one workgroup per problem.  A sample occupies a group of LPT = 16 / 32 / 64 lanes (dgp_group::lanes_for(N_d), as dgp_gp_interpolate), 64 / LPT samples per
 // wavefront, up to kMaxWaves wavefronts; more samples than the workgroup has groups are walked in passes.  The dense check of a sample is dgp_dense_walk.h's -- the
 // walk and the butterflies gp_interpolate.hip runs, so sample_summary is dgp_gp_interpolate's summary bit for bit.  Lane 0 of a group parks (tier, max penetration,
 // score, status) of its sample in LDS (24 bytes per sample, sized by the launch); after one barrier thread s counts the samples that precede sample s -- its rank, a
@@ -34,7 +34,7 @@ constexpr int kMaxSamples = 1024;   // 24 KB of keys in LDS
 struct SelectShape { int lpt, waves, passes; };
 inline SelectShape select_shape(int nd, int num_samples) {
   SelectShape sh;
-  sh.lpt = dgp_host::dense_lpt(nd);
+  sh.lpt = dgp_group::lanes_for(nd);
   const int tpw = 64 / sh.lpt;
   const int need = (num_samples + tpw - 1) / tpw;
   sh.waves = need < kMaxWaves ? need : kMaxWaves;
@@ -169,15 +169,6 @@ __global__ void __launch_bounds__(64 * kMaxWaves) select_samples_kernel(const Se
   else copy_words<uint32_t>(src, dst, bytes, tid, nthreads);      // (fp32 rows off an 8-byte boundary; a row is a whole number of 8-byte pairs)
 }
 
-template <int DOF, typename IO>
-hipError_t launch_lpt(const SelectShape& sh, const SelectArgs& a, hipStream_t s, const dgp_dev::Events& ev) {
-  const dim3 grid((unsigned)a.p.B), block((unsigned)(64 * sh.waves));
-  const unsigned lds = (unsigned)(a.S * (2 * sizeof(double) + 2 * sizeof(int)));
-  if (sh.lpt == 16) return dgp_dev::launch(select_samples_kernel<DOF, IO, 16>, grid, block, lds, s, ev, a);
-  if (sh.lpt == 32) return dgp_dev::launch(select_samples_kernel<DOF, IO, 32>, grid, block, lds, s, ev, a);
-  return dgp_dev::launch(select_samples_kernel<DOF, IO, 64>, grid, block, lds, s, ev, a);
-}
-
 }  // namespace
 
 extern "C" int dgp_select_samples(const DgpHandle* h, int32_t batch, int32_t num_samples, const void* th, const void* score, const int32_t* exclude, const DgpSdf* sdf,
@@ -215,10 +206,12 @@ extern "C" int dgp_select_samples(const DgpHandle* h, int32_t batch, int32_t num
   a.lim = dgp_dense::Limits{h->cfg.x_lims[0], h->cfg.x_lims[1], h->cfg.y_lims[0], h->cfg.y_lims[1]};
   a.S = num_samples; a.sample_major = sp->sample_major != 0 ? 1 : 0; a.require_inside = sp->require_inside != 0 ? 1 : 0;
   const SelectShape sh = select_shape(a.nd, num_samples);
+  const dim3 grid((unsigned)a.p.B), block((unsigned)(64 * sh.waves));
+  const unsigned lds = (unsigned)(a.S * (2 * sizeof(double) + 2 * sizeof(int)));
   hipStream_t s = (hipStream_t)stream;
-  const bool f64 = h->cfg.io_dtype == DGP_F64;
-  const hipError_t e = h->cfg.dof == 2 ? (f64 ? launch_lpt<2, double>(sh, a, s, ev) : launch_lpt<2, float>(sh, a, s, ev))
-                                       : (f64 ? launch_lpt<3, double>(sh, a, s, ev) : launch_lpt<3, float>(sh, a, s, ev));
+  const hipError_t e = dgp_dev::with_dof_io(h->cfg.dof, h->cfg.io_dtype == DGP_F64, [&](auto dof, auto io) {
+    return dgp_dev::with_lpt(sh.lpt, [&](auto L) { return dgp_dev::launch(select_samples_kernel<dof, decltype(io), L>, grid, block, lds, s, ev, a); });
+  });
   return dgp_dev::hip_rc(e, "dgp_select_samples");
 }
 

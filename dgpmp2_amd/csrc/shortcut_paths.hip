@@ -3,7 +3,8 @@
 // What it stands in for: the simplifySolution() call RRTStar.plan makes before interpolate(num_states) (diff_gpmp2/ompl_rrtstar.py:36-41): the trajectory the
 // reference's Gauss-Newton receives is a short any-angle polyline, not a tree path.  Here: one greedy pass of string pulling over the vertices start -> traced
 // cells -> goal, a segment being usable where every point of OMPL's discrete motion check is feasible by Env2D.is_feasible -- the sampler's bilinear distance
-// (csrc/problem_sampler.hip, restated below for row-major grids: the same pixel coordinates, clamps, weights and operation order) above the clearance.
+// (csrc/problem_sampler.hip, restated below for row-major grids: the same pixel coordinates, clamps, weights and operation order -- lifted into one function the
+// distance leaves shortcut_paths_kernel as it is but recompiles sample_problems_kernel<double> to code measured 0.5 % slower) above the clearance.
 // include/dgpmp2_hip.h states the rule, tests/shortcut_oracle.py restates it, and the kernel is held against that bit for bit.
 //
 // Mapping: one wavefront (one workgroup of 64) per problem, as init_paths.hip.  The hot path is visible(P, Q): the M + 1 check points of a segment go over the 64
@@ -221,21 +222,13 @@ extern "C" int dgp_shortcut_paths(const DgpHandle* h, int32_t batch, const DgpSd
                                   const void* goal, const int32_t* path_cells, const int32_t* num_cells, void* th, int32_t* vertex_index, int32_t* num_vertices,
                                   double* length, int32_t* info, void* stream) {
   const dgp_dev::Events ev = dgp_dev::take_events();
-  if (!h) return fail(DGP_EINVAL, "null handle");
-  const DgpConfig& c = *reinterpret_cast<const DgpConfig*>(h);      // DgpHandle's first member (dgp_host.h holds that with a static_assert); this unit needs nothing else of it
-  if (c.dof != 2) return fail(DGP_EINVAL, "dgp_shortcut_paths: only dof == 2 (2-D point-robot problems), got %d", c.dof);
-  if (!p) return fail(DGP_EINVAL, "dgp_shortcut_paths: null DgpShortcutParams");
-  if (!sdf || !sdf->data) return fail(DGP_EINVAL, "dgp_shortcut_paths: sdf must be non-null");
-  if (!start || !goal || !path_cells || !num_cells || !th)
-    return fail(DGP_EINVAL, "dgp_shortcut_paths: start, goal, path_cells, num_cells and th must be non-null device pointers");
-  if (batch < 1) return fail(DGP_EINVAL, "dgp_shortcut_paths: batch must be positive, got %d", batch);
-  if (sdf->layout == DGP_SDF_TILED4) return fail(DGP_EINVAL, "dgp_shortcut_paths: tiled grids (DGP_SDF_TILED4) are not implemented here: pass the row-major grid");
-  if (sdf->layout != DGP_SDF_ROWMAJOR) return fail(DGP_EINVAL, "dgp_shortcut_paths: bad DgpSdf::layout %d", sdf->layout);
-  if (sdf->rows < 1 || sdf->cols < 1 || sdf->rows > MAX_SIDE || sdf->cols > MAX_SIDE)
-    return fail(DGP_EINVAL, "dgp_shortcut_paths: grid sides must be in 1..%d, got %dx%d", MAX_SIDE, sdf->rows, sdf->cols);
-  if (sdf->batch_stride < 0) return fail(DGP_EINVAL, "dgp_shortcut_paths: negative sdf batch stride");
+  dgp_dev::RowMajorGrid g;
+  const int rc = dgp_dev::rowmajor_grid("dgp_shortcut_paths", h, batch, sdf, p, "DgpShortcutParams", start && goal && path_cells && num_cells && th,
+                                        "start, goal, path_cells, num_cells and th", MAX_SIDE, g);
+  if (rc != DGP_OK) return rc;
+  const DgpConfig& c = *g.cfg;
   if (!(p->clearance == p->clearance)) return fail(DGP_EINVAL, "dgp_shortcut_paths: NaN clearance");
-  const double res = (c.x_lims[1] - c.x_lims[0]) / (double)sdf->cols;      // the lookup's (dgp_host::fill_call)
+  const double res = g.res;
   if (!(p->check_step - p->check_step == 0.0) || !(p->check_step >= res / 16.0))
     return fail(DGP_EINVAL, "dgp_shortcut_paths: check_step must be finite and >= res / 16 = %g, got %g", res / 16.0, p->check_step);
   if (p->path_cap < 1 || p->path_cap > MAX_PATH_CAP) return fail(DGP_EINVAL, "dgp_shortcut_paths: path_cap must be in 1..%d, got %d", MAX_PATH_CAP, p->path_cap);
@@ -247,9 +240,7 @@ extern "C" int dgp_shortcut_paths(const DgpHandle* h, int32_t batch, const DgpSd
   a.env_index = env_index; a.start = start; a.goal = goal; a.path_cells = path_cells; a.num_cells = num_cells; a.th = th;
   a.vertex_index = vertex_index; a.num_vertices = num_vertices; a.info = info; a.length = length;
   a.clearance = p->clearance; a.check_step = p->check_step;
-  a.res = res; a.inv_res = 1.0 / res;
-  a.orig_x = (0. - c.x_lims[0] / a.res);
-  a.orig_y = (0. - c.y_lims[0] / a.res);
+  a.res = res; a.inv_res = 1.0 / res; a.orig_x = g.orig_x; a.orig_y = g.orig_y;
   a.total_time_sec = c.total_time_sec;
   a.max_d = c.x_lims[1] - c.x_lims[0];      // Env2D.MAX_D: the distance of a point outside the limits
   a.xlo = c.x_lims[0]; a.xhi = c.x_lims[1]; a.ylo = c.y_lims[0]; a.yhi = c.y_lims[1];

@@ -21,6 +21,8 @@
 #include <stdint.h>
 #include "dgp_status.h"
 #include "dgp_launch.h"
+#include "dgp_group.h"
+#include "dgp_rowio.h"
 
 #pragma clang fp contract(off)
 
@@ -50,10 +52,11 @@ constexpr int kBatchLanes = 1024;                // loss_batch's workgroup
 constexpr int kBwdLanes = 256;
 constexpr int kBwdMaxBlocks = 1 << 16;           // the rest of the rows in the grid-stride loop
 
-// bytes of the vector a row of D elements is moved in: 16, or 8 for the 24-byte row (d = 6, fp32) whose every second row sits off the 16-byte boundary
-template <typename IO, int D>
-constexpr int vec_bytes() { return (D * sizeof(IO)) % 16 == 0 ? 16 : 8; }
+using dgp_group::group_sum;
+using dgp_rowio::vec_bytes;
 
+// dgp_rowio.h's rule and accesses in this unit's own wording (ext_vector_type, VEC a template flag): through dgp_rowio's load_row / store_row the sixteen vector
+// kernels here compile to other code, and loss_rows<2, double, 16> then measured one 40 ns event tick above the range of this code's own repeated medians.
 template <typename IO, int D, bool VEC>
 __device__ __forceinline__ void load_row(const IO* p, IO (&r)[D]) {
   if (VEC) {
@@ -103,13 +106,6 @@ __device__ __forceinline__ void row_miss(const IO* upd, const IO* tgt, const IO*
 #pragma unroll
     for (int c = 0; c < D; ++c) m[c] = (double)u[c] - (double)t[c];
   }
-}
-
-template <int LPT>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
-  return v;
 }
 
 template <int DOF, typename IO, int LPT, bool VEC>
@@ -227,7 +223,8 @@ __global__ void __launch_bounds__(kBwdLanes) loss_backward(const LossBwdArgs a) 
   }
 }
 
-// lanes per trajectory of loss_rows: from the number of states alone
+// lanes per trajectory of loss_rows: from the number of states alone.  Its own thresholds (one state per lane up to 32 states), not dgp_group::lanes_for's: the
+// butterfly order, and so the bits of per_traj, follow from them (tests/loss_oracle.py mirrors this rule).
 int rows_lpt(int n) { return n <= 16 ? 16 : n <= 32 ? 32 : 64; }
 
 bool aligned(const void* p, int bytes) { return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }      // (null counts as aligned)
@@ -236,9 +233,7 @@ template <int DOF, typename IO, bool VEC>
 hipError_t launch_rows(const LossArgs& a, hipStream_t s, const dgp_dev::Events& ev) {
   const int lpt = rows_lpt(a.n), tpw = 64 / lpt;
   const dim3 grid((unsigned)(((int64_t)a.B + tpw - 1) / tpw)), block(64);
-  if (lpt == 16) return dgp_dev::launch(loss_rows<DOF, IO, 16, VEC>, grid, block, 0, s, ev, a);
-  if (lpt == 32) return dgp_dev::launch(loss_rows<DOF, IO, 32, VEC>, grid, block, 0, s, ev, a);
-  return dgp_dev::launch(loss_rows<DOF, IO, 64, VEC>, grid, block, 0, s, ev, a);
+  return dgp_dev::with_lpt(lpt, [&](auto L) { return dgp_dev::launch(loss_rows<DOF, IO, L, VEC>, grid, block, 0, s, ev, a); });
 }
 
 template <int DOF, typename IO>
@@ -285,9 +280,7 @@ extern "C" int dgp_step_loss(int32_t dtype, int32_t batch, int32_t num_states, i
   a.unw_sg = unw_sg; a.unw_gp = unw_gp; a.unw_obs = unw_obs;
   a.per_traj = per_traj; a.terms = terms; a.w = *w; a.B = batch; a.n = num_states;
   hipStream_t s = (hipStream_t)stream;
-  const bool f64 = dtype == DGP_F64;
-  const hipError_t e = dof == 2 ? (f64 ? launch_forward<2, double>(a, s, ev) : launch_forward<2, float>(a, s, ev))
-                                : (f64 ? launch_forward<3, double>(a, s, ev) : launch_forward<3, float>(a, s, ev));
+  const hipError_t e = dgp_dev::with_dof_io(dof, dtype == DGP_F64, [&](auto DOF, auto io) { return launch_forward<DOF, decltype(io)>(a, s, ev); });
   return dgp_dev::hip_rc(e, "dgp_step_loss");
 }
 
@@ -304,8 +297,6 @@ extern "C" int dgp_step_loss_backward(int32_t dtype, int32_t batch, int32_t num_
   a.g_unw_sg = g_unw_sg; a.g_unw_gp = g_unw_gp; a.g_unw_obs = g_unw_obs;
   a.w = *w; a.B = batch; a.n = num_states;
   hipStream_t s = (hipStream_t)stream;
-  const bool f64 = dtype == DGP_F64;
-  const hipError_t e = dof == 2 ? (f64 ? launch_backward<2, double>(a, s, ev) : launch_backward<2, float>(a, s, ev))
-                                : (f64 ? launch_backward<3, double>(a, s, ev) : launch_backward<3, float>(a, s, ev));
+  const hipError_t e = dgp_dev::with_dof_io(dof, dtype == DGP_F64, [&](auto DOF, auto io) { return launch_backward<DOF, decltype(io)>(a, s, ev); });
   return dgp_dev::hip_rc(e, "dgp_step_loss_backward");
 }

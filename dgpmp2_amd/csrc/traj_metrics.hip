@@ -21,6 +21,7 @@
 #endif
 #include "dgp_host.h"
 #include "dgp_launch.h"
+#include "dgp_group.h"
 
 namespace {
 
@@ -36,18 +37,9 @@ struct MetricsArgs {
 };
 static_assert(sizeof(MetricsArgs) <= 4096, "kernel-argument segment");
 
-template <int LPT>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-template <int LPT>
-__device__ __forceinline__ int group_sum_i(int v) {
-#pragma unroll
-  for (int m = 1; m < LPT; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
+using dgp_group::group_sum;
+using dgp_group::group_sum_i;
+
 // torch.max: a NaN wins
 __device__ __forceinline__ double max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
 template <int LPT>
@@ -150,15 +142,6 @@ __global__ void __launch_bounds__(64) traj_metrics_kernel(const MetricsArgs a) {
   if (on && l < DGP_METRIC_COUNT) a.metrics[b * DGP_METRIC_COUNT + l] = out;
 }
 
-template <int DOF, typename IO>
-hipError_t launch_lpt(int lpt, const MetricsArgs& a, hipStream_t s, const dgp_dev::Events& ev) {
-  const int tpw = 64 / lpt;
-  const dim3 grid((unsigned)((a.p.B + tpw - 1) / tpw)), block(64);
-  if (lpt == 16) return dgp_dev::launch(traj_metrics_kernel<DOF, IO, 16>, grid, block, 0, s, ev, a);
-  if (lpt == 32) return dgp_dev::launch(traj_metrics_kernel<DOF, IO, 32>, grid, block, 0, s, ev, a);
-  return dgp_dev::launch(traj_metrics_kernel<DOF, IO, 64>, grid, block, 0, s, ev, a);
-}
-
 }  // namespace
 
 extern "C" int dgp_traj_metrics(const DgpHandle* h, int32_t batch, const void* th, const DgpSdf* sdf, double metric_eps, const void* th_opt,
@@ -171,10 +154,11 @@ extern "C" int dgp_traj_metrics(const DgpHandle* h, int32_t batch, const void* t
   if (metrics && a.p.n < 3) return fail(DGP_EINVAL, "dgp_traj_metrics: the metrics need num_states >= 3 (no interior state), got %d", a.p.n);
   a.th_opt = th_opt; a.metrics = metrics; a.obs_error = obs_error;
   a.eps = metric_eps; a.total_time_sec = h->cfg.total_time_sec;
-  const int lpt = a.p.n <= 64 ? 16 : (a.p.n <= 128 ? 32 : 64);
+  const int lpt = dgp_group::lanes_for(a.p.n), tpw = 64 / lpt;
+  const dim3 grid((unsigned)((a.p.B + tpw - 1) / tpw)), block(64);
   hipStream_t s = (hipStream_t)stream;
-  const bool f64 = h->cfg.io_dtype == DGP_F64;
-  const hipError_t e = h->cfg.dof == 2 ? (f64 ? launch_lpt<2, double>(lpt, a, s, ev) : launch_lpt<2, float>(lpt, a, s, ev))
-                                       : (f64 ? launch_lpt<3, double>(lpt, a, s, ev) : launch_lpt<3, float>(lpt, a, s, ev));
+  const hipError_t e = dgp_dev::with_dof_io(h->cfg.dof, h->cfg.io_dtype == DGP_F64, [&](auto dof, auto io) {
+    return dgp_dev::with_lpt(lpt, [&](auto L) { return dgp_dev::launch(traj_metrics_kernel<dof, decltype(io), L>, grid, block, 0, s, ev, a); });
+  });
   return dgp_dev::hip_rc(e, "dgp_traj_metrics");
 }
